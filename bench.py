@@ -6,9 +6,13 @@ A "step" = one full training step of the reference loop body (DenseBox.py:2016-2
 gradient all-reduce over RCCL (N>1), fused SGD.  Workload = BASELINE.json configs[2]/[3]: DenseBoxLMLOC (the net
 the reference's __main__ trains: score + bbox + landmark heat-maps + landmark offsets + refine), batch 64 per GPU,
 f16 compute (--dtype bf16 for configs[3]'s type; same MFMA rate) / fp32 accumulate / fp32 master weights.  Weak scaling:
-per-GPU batch fixed.  The line also carries the bf16 step rate (`bf16`) and the inference half of the metric (`inference`).
+per-GPU batch fixed.  A plain run sets up, warms up, times --steps steps and prints the line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...).  With --full the line also carries the roofline of the dominant kernel family,
+the achieved forward tolerance, the other 16-bit type's step rate (`bf16`), the inference half of the metric (`inference`) and the
+CPU baseline.  --dump-outputs DIR writes what the last timed step computed (loss, parameter gradients, updated parameters) as .npy.
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -70,11 +74,16 @@ def host_cpu():
 
 def cpu_baseline(kind, seconds=20.0):
     """Reference algorithm on the host cores: the CPU oracle (torch fp32 nn ops + numpy bookkeeping) running the same
-    training step on a bounded sample (batch 8, >= 5 timed steps), torch threads = the host's physical cores.  Reported baseline,
-    not a target."""
+    training step on a bounded sample (batch 8, >= 5 timed steps), torch threads = the host's physical cores (at most the CPUs this
+    process may use).  Reported baseline, not a target."""
     from oracle import densebox_oracle as O
     cpu = host_cpu()
     threads = cpu['physical_cores'] or torch.get_num_threads()
+    # never more threads than the CPUs this process may run on (a share of a larger host) or OMP_NUM_THREADS asks for
+    avail = [len(os.sched_getaffinity(0))] if hasattr(os, 'sched_getaffinity') else []
+    if os.environ.get('OMP_NUM_THREADS', '').isdigit() and int(os.environ['OMP_NUM_THREADS']) > 0:
+        avail.append(int(os.environ['OMP_NUM_THREADS']))
+    threads = min([threads] + avail)
     torch.set_num_threads(int(threads))
     n = 8
     net = getattr(D, kind)(synth.vgg19_standin(seed=0))
@@ -267,6 +276,24 @@ def inference(kind, dev):
             'value': res['512x512']['img_per_s'], 'unit': 'img/s at 512x512', 'sizes': res}
 
 
+DUMP_MAX_ELEMS = 4 << 20        # per flat vector: 16 MB in fp32, the three files well under 64 MB in all
+
+
+def dump_outputs(path, loss, net, dp):
+    """What the last timed step handed its caller: the loss, the all-reduced parameter gradients (the flat buffer the update read) and
+    the updated parameters (named_parameters order, flattened), as .npy (the loss fp64, the rest fp32).  A flat vector longer than
+    DUMP_MAX_ELEMS is written as the fixed sample at the sorted positions RandomState(0) draws (the same in every run of the same net)."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'loss.npy'), np.asarray([float(loss.detach())], np.float64))
+    flats = {'grad': dp.reducer.flat.detach(),
+             'param': torch.cat([p.detach().reshape(-1).float() for _, p in net.named_parameters()])}
+    for name, v in flats.items():
+        if v.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.RandomState(0).choice(v.numel(), DUMP_MAX_ELEMS, replace=False))
+            v = v[torch.from_numpy(idx).to(v.device)]
+        np.save(os.path.join(path, name + '.npy'), v.float().cpu().numpy())
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one rank per GPU."""
     import socket
@@ -322,9 +349,15 @@ def main():
     ap.add_argument('--dtype', default='f16', choices=['bf16', 'f16', 'f32'],
                     help='compute dtype; f16 = BASELINE configs[1]/[2] and 10x closer to the reference than bf16 (profiles/r02_lowprec_errors.json)')
     ap.add_argument('--batch', type=int, default=64, help='patches per GPU')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: roofline (3 extra profiled steps, library GEMM / copy peaks), '
+                         'achieved tolerance vs the reference fixture, the other 16-bit type, inference, CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last one computed as DIR/<name>.npy: loss, parameter gradients and '
+                         'updated parameters (loss fp64, the rest fp32; a fixed seeded sample of the flat vectors when they exceed the size cap)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     ap.add_argument('--cpu-seconds', type=float, default=20.0)
-    ap.add_argument('--no-inference', action='store_true')
+    ap.add_argument('--no-inference', action='store_true', help='--full without inference and the other 16-bit type')
     ap.add_argument('--dry-run', action='store_true', help='launcher / rendezvous only: no GPU work (CPU test of the N>1 launch path)')
     args = ap.parse_args()
 
@@ -364,6 +397,9 @@ def run(args):
     dev = torch.device('cuda', local)
     preflight(dev)                                     # first collective under a watchdog: a broken RCCL set-up reports instead of hanging
     kind, n = args.kind, args.batch
+    # the step's dropout masks are a counter-based hash seeded from torch.initial_seed() (engine._next_drop_seed): a fixed seed makes
+    # every run with the same arguments see the same inputs, so that two builds can be compared output for output (--dump-outputs)
+    torch.manual_seed(0)
 
     net = getattr(D, kind)(synth.vgg19_standin(seed=0))
     synth.fill_params_(net, 11)
@@ -425,20 +461,43 @@ def run(args):
     gflat = dp.reducer.flat
     assert bool(torch.isfinite(gflat).all()), 'non-finite parameter gradient in %s training' % args.dtype
     grad_absmax = float(gflat.abs().max())
-
-    # ---- roofline of the dominant kernel, measured live with HIP events on the launch stream: 3 extra, untimed steps.
-    # EVERY rank runs them (they contain collectives); only rank 0 records events.
-    eng = net.engine()
-    if rank == 0:
-        eng.profile = []
-    for _ in range(3):
-        one_step()
-    barrier()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, net, dp)
 
     out = None
     if rank == 0:
         ms = dt / args.steps * 1e3
         value = n * world * args.steps / dt
+        out = {
+            'metric': 'training patches/sec (240x240)', 'value': round(value, 1), 'unit': 'patches/s',
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms, 3),
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': args.dtype, 'data': 'synthetic',
+            'config': {'workload': 'full training step (fwd + fused dense loss w/ hard-negative mining + bwd + grad '
+                                   'all-reduce + SGD) of %s on 240x240 patches' % kind,
+                       'net': kind, 'batch_per_gpu': n, 'global_batch': n * world, 'patch': '240x240',
+                       'parallelism': 'dp%d' % world, 'half_neg': half, 'loss': round(loss_val, 2),
+                       'grad_finite': True, 'grad_absmax': round(grad_absmax, 3),
+                       'f16_overflow_guard': {'on': bool(dp.guard_f16 and args.dtype == 'f16'), 'skipped_steps': dp.skipped_steps()}},
+            'step_tflops_per_gpu': round(n * STEP_GFLOP[kind] / (ms * 1e-3) / 1e3, 1),
+            # the live process group the gradient all-reduce ran on ("nccl" is RCCL on ROCm): lets a scaling run be checked for
+            # "RCCL saw N ranks"
+            'rccl': {'backend': dist.get_backend() if dist.is_initialized() else None,
+                     'world': dist.get_world_size() if dist.is_initialized() else 1,
+                     'collective': bool(dp.reducer.collective), 'bucket_bytes': int(dp.reducer.bucket_elems * 4)},
+            'full': bool(args.full),
+        }
+
+    # ---- --full only: roofline of the dominant kernel, measured live with HIP events on the launch stream: 3 extra, untimed steps.
+    # EVERY rank runs them (they contain collectives); only rank 0 records events.
+    if args.full:
+        eng = net.engine()
+        if rank == 0:
+            eng.profile = []
+        for _ in range(3):
+            one_step()
+        barrier()
+
+    if rank == 0 and args.full:
         calls = eng.profile
         eng.profile = None
         fam = {}
@@ -476,32 +535,15 @@ def run(args):
         # (the ws kernel template serves 3x3 layers <T,WM,3,EPIK> and the 1x1 head GEMMs <T,1,1,EPIK>: only the former belong here)
         roof['stack_3x3'] = {'fwd_dgrad': agg(is3),
                              'with_wgrad': agg(lambda k: is3(k) or k.startswith(('wgrad_all9', 'wgrad_row3', 'wgrad3x3')))}
-        out = {
-            'metric': 'training patches/sec (240x240)', 'value': round(value, 1), 'unit': 'patches/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms, 3),
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': args.dtype,
-            'tolerance': achieved_tolerance(kind, args.dtype, dev), 'data': 'synthetic',
-            'config': {'workload': 'full training step (fwd + fused dense loss w/ hard-negative mining + bwd + grad '
-                                   'all-reduce + SGD) of %s on 240x240 patches' % kind,
-                       'net': kind, 'batch_per_gpu': n, 'global_batch': n * world, 'patch': '240x240',
-                       'parallelism': 'dp%d' % world, 'half_neg': half, 'loss': round(loss_val, 2),
-                       'grad_finite': True, 'grad_absmax': round(grad_absmax, 3),
-                       'f16_overflow_guard': {'on': bool(dp.guard_f16 and args.dtype == 'f16'), 'skipped_steps': dp.skipped_steps()}},
-            'step_tflops_per_gpu': round(n * STEP_GFLOP[kind] / (ms * 1e-3) / 1e3, 1),
-            'roofline': roof,
-            # the live process group the gradient all-reduce ran on ("nccl" is RCCL on ROCm): lets a scaling run be checked for
-            # "RCCL saw N ranks"
-            'rccl': {'backend': dist.get_backend() if dist.is_initialized() else None,
-                     'world': dist.get_world_size() if dist.is_initialized() else 1,
-                     'collective': bool(dp.reducer.collective), 'bucket_bytes': int(dp.reducer.bucket_elems * 4)},
-        }
+        out['tolerance'] = achieved_tolerance(kind, args.dtype, dev)
+        out['roofline'] = roof
         mp = measured_peaks(dev, args.dtype)
         roof['measured_peak'] = mp
         roof['frac_of_measured_gemm'] = round(ach / mp['library_gemm_8192_tflops'], 4)
         out['roofline']['traffic_source'] = 'profiles/%s (null unless collected on these kernel sources)' % PMC_FILE
     # the other 16-bit type on the same workload (configs[3] names bf16): a short secondary measurement, every rank takes part
     other = {'f16': 'bf16', 'bf16': 'f16'}.get(args.dtype)
-    if other and not args.no_inference:
+    if args.full and other and not args.no_inference:
         net.compute_dtype = other
         for _ in range(3):
             one_step()
@@ -514,7 +556,7 @@ def run(args):
         net.compute_dtype = args.dtype
         if rank == 0:
             out[other] = {'value': round(n * world * 10 / dt2, 1), 'unit': 'patches/s', 'ms_per_step': round(dt2 / 10 * 1e3, 3), 'steps': 10}
-    if rank == 0:
+    if rank == 0 and args.full:
         if not args.no_inference:
             out['inference'] = inference(kind, dev)
         if world == 1 and not args.no_cpu_baseline:

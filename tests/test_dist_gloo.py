@@ -1,4 +1,4 @@
-"""world_size-2 CPU (gloo) tests of the data-parallel layer: flat-buffer bucketed all-reduce, the global positive
+"""world_size-2 CPU (gloo) tests (and world size 8's sharding algebra in one process) of the data-parallel layer: flat-buffer bucketed all-reduce, the global positive
 count, and the algebra that makes N ranks equal one rank on the concatenated batch (DenseBox.py:2074, :2917)."""
 import os
 import socket
@@ -149,3 +149,36 @@ def _loss_case(rank, world):
 
 def test_sharded_loss_equals_global_loss():
     _run(_loss_case)
+
+
+def test_world_8_rank_shards_sum_to_the_global_loss():
+    """configs[3]'s world size on the CPU, in ONE process (each rank's shard in turn; the all-reduces are SUMs): the positive count
+    of eight rank slices, the mining constants, and the eight sharded losses == the loss of the concatenated batch, per-sample
+    gradients and mined indices slice by slice."""
+    kind, n, world = 'DenseBoxLMLOC', 3, 8
+    N = n * world
+    rs = np.random.RandomState(7)
+    shapes = [(N, 1), (N, 1), (N, 4), (N, 4), (N, 8)]
+    outs = [torch.from_numpy(rs.randn(s[0], s[1], 60, 60).astype(np.float32) * 3) for s in shapes]
+    bbox, vert, lab = synth.synth_labels(N, seed=11, neg_frac=0.34)
+    P = int(LB.positive_count(bbox, lab).sum())
+    slices = [slice(r * n, (r + 1) * n) for r in range(world)]
+    assert sum(int(LB.positive_count(bbox[sl], lab[sl]).sum()) for sl in slices) == P > 0
+    _, half = LB.neg_counts(P, N)
+    rn = synth.synth_rand_neg_indices(N, half, seed=1).numpy()
+    lrn = synth.synth_rand_neg_indices(4 * N, 1, seed=2).reshape(4, N, 1).numpy()
+    full = [o.clone().requires_grad_(True) for o in outs]
+    res = O.loss_step(kind, tuple(full), bbox.numpy(), vert.numpy(), lab.numpy(), rand_neg=rn, lm_rand_neg=lrn)
+    res['loss'].backward()
+    tot = torch.zeros((), dtype=torch.float64)
+    for sl in slices:
+        mine = [o[sl].clone().requires_grad_(True) for o in outs]
+        r = O.loss_step(kind, tuple(mine), bbox.numpy()[sl], vert.numpy()[sl], lab.numpy()[sl], rand_neg=rn[sl],
+                        lm_rand_neg=lrn[:, sl], batch_global=N, positive_num_global=P)
+        assert r['half'] == half
+        r['loss'].backward()
+        tot += r['loss'].detach().double()
+        for a, b in zip(mine, full):
+            assert torch.allclose(a.grad, b.grad[sl], rtol=0, atol=0)
+        assert np.array_equal(r['neg_idx'], res['neg_idx'][sl])
+    assert torch.isclose(tot, res['loss'].detach().double(), rtol=1e-6)

@@ -1,7 +1,7 @@
-"""GPU data-parallel equivalence: WORLD ranks (2 and 8 = configs[3]'s world size; gloo transport, all on cuda:0 -- RCCL needs one
-device per rank, the reducer/step logic is backend-agnostic) each train on their slice of a batch; parameters after the step must
-equal the single-process step on the concatenated batch, and every rank must hold the same parameters (sum-loss => all-reduce SUM without division; global
-positive count => identical mining constants)."""
+"""GPU data-parallel equivalence: WORLD ranks (2 and 8 = configs[3]'s world size; gloo transport, rank r on device r % device_count:
+world 2 shares cuda:0 -- RCCL needs one device per rank, the reducer/step logic is backend-agnostic) each train on their slice of a
+batch; parameters after the step must equal the single-process step on the concatenated batch, and every rank must hold the same
+parameters (sum-loss => all-reduce SUM without division; global positive count => identical mining constants)."""
 import os
 import socket
 
@@ -45,7 +45,7 @@ def _rank_main(rank, world, port, out_path):
     if world > 2:
         import time
         time.sleep(0.3 * rank)           # one device context after the other (see tests/test_zz_world8.py)
-    torch.cuda.set_device(0)
+    torch.cuda.set_device(rank % torch.cuda.device_count())
     dist.init_process_group('gloo', rank=rank, world_size=world)
     try:
         from densebox_amd.dist import DataParallel
@@ -73,37 +73,11 @@ def _rank_main(rank, world, port, out_path):
         dist.destroy_process_group()
 
 
-def run_ranks_equal_one_process(tmp_path, WORLD, attempts=1):
-    """Retries ONLY a rank killed by a signal (eight device contexts time-slicing one virtual device died in driver code about once in
-    three runs: ProcessExitedException with a signal, no Python exception).  An exception RAISED inside a rank -- the in-rank assertions
-    ('ranks diverged after one step', the global positive count) or any error the library reports -- is a real failure and propagates
-    at once.  More than one attempt is reported as a warning with the signal of every retried run."""
-    import time
-    import warnings
-    from torch.multiprocessing import ProcessExitedException
-    retried = []
-    out = None
-    for attempt in range(attempts):
-        s = socket.socket(); s.bind(('127.0.0.1', 0)); port = s.getsockname()[1]; s.close()
-        out = str(tmp_path / ('dp%d.pt' % attempt))
-        try:
-            mp.spawn(_rank_main, args=(WORLD, port, out), nprocs=WORLD, join=True)
-            break
-        except ProcessExitedException as e:
-            sig = getattr(e, 'signal_name', None)
-            if sig is None or attempts == 1:                # a non-zero exit code without a signal is the rank's own doing: no retry
-                raise
-            retried.append('attempt %d: rank %s killed by %s' % (attempt, getattr(e, 'error_index', '?'), sig))
-            out = None
-            time.sleep(5.0)                                 # (the dead ranks' device contexts are torn down asynchronously: failures came in streaks)
-    if out is None:
-        # Measured in round 5 (gpurun_w8.sh: nine runs under three kernel selections, incl. DBX_WS=0 DBX_P8=0 = round 1's LDS kernels
-        # only): ~40 % of all eight-rank attempts on ONE virtual GPU die in driver code (HSA_STATUS_ERROR_ILLEGAL_INSTRUCTION or a memory
-        # fault in torch's fill kernel) whatever kernels the step uses, while worlds of one and two never do -- the box cannot time-slice
-        # eight contexts reliably.  Reported, never counted as a pass.
-        pytest.xfail('world-%d run: every one of %d attempts was killed by a signal (%s)' % (WORLD, attempts, '; '.join(retried)))
-    if retried:
-        warnings.warn('world-%d run needed %d attempts (%s)' % (WORLD, len(retried) + 1, '; '.join(retried)))
+def run_ranks_equal_one_process(tmp_path, WORLD):
+    """WORLD ranks (one spawn, no retry: a rank that dies fails the test) against one process on the concatenated batch."""
+    s = socket.socket(); s.bind(('127.0.0.1', 0)); port = s.getsockname()[1]; s.close()
+    out = str(tmp_path / 'dp.pt')
+    mp.spawn(_rank_main, args=(WORLD, port, out), nprocs=WORLD, join=True)
     got = torch.load(out)
     # single process, concatenated batch
     from densebox_amd.optim import SGD

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 tag=$1; dt=${2:-f16}
 mkdir -p $(dirname $R/gpurun_out/$tag)
-B="python $R/bench.py --dtype $dt --no-cpu-baseline --no-inference"
+B="python $R/bench.py --dtype $dt --full --no-cpu-baseline --no-inference"
 rm -rf /tmp/cp_*
 rocprofv3 --kernel-trace -d /tmp/cp_kt -o k -- $B --steps 10 --warmup 5 > /tmp/cp_kt.log 2>&1
 DB=$(find /tmp/cp_kt -name "*.db" | head -1)
