@@ -132,10 +132,12 @@ SIGNATURES = {
     'dbx_sgd_pack_step_guarded': (C.c_int, [_I32, _VP, _I32, _I64, _VP, _F, _F, _F, _I32, _VP, _I32, _VP]),
     'dbx_detect_scratch_bytes': (_I64, [_I32, _I32, _I32]),
     'dbx_detect': (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _D, _VP, _I32, _VP, _VP, _VP, _VP]),
+    'dbx_detect_batch_scratch_bytes': (_I64, [_I32, _I32, _I32, _I32]),
+    'dbx_detect_batch': (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _D, _VP, _I32, _VP, _VP, _VP, _VP]),
     'dbx_nms': (C.c_int, [_VP, _I32, _I32, _D, _VP, _VP, _VP]),
 }
 
-ABI_VERSION = 7          # include/densebox_hip.h DBX_ABI_VERSION this binding was written against
+ABI_VERSION = 8          # include/densebox_hip.h DBX_ABI_VERSION this binding was written against
 _lib = None
 MISSING = []
 

@@ -239,10 +239,13 @@ __device__ void nms_block(const double* dets, int n, int dc, double thresh, int*
     if (tid == 0) keep[0] = cnt;
 }
 
+// image 0's maps, outputs and scratch slice; workgroup b reads [b][C][rows][cols] maps, writes dets[b], topk[b], keep[b] and works
+// in the scratch slice `scratch_stride` bytes further on per image (a multiple of 256: the slices keep image 0's alignment)
 struct DetArgs {
     const float* score; const float* loc; const float* lm_heat; const float* lm_loc;
     int rows, cols, K, dc; double thresh;
     double* dets; long long* topk; int* keep; float* work; int* order; unsigned char* supp; unsigned long long* mask;
+    long long scratch_stride;
 };
 
 // order-preserving key of a score for the radix select: larger float <-> larger key, -0 == +0, NaN below every number
@@ -258,7 +261,24 @@ __device__ __forceinline__ unsigned det_key(float v) {
 #ifndef DET_SELECT_MIN_K
 #define DET_SELECT_MIN_K 49
 #endif
-__global__ __launch_bounds__(DET_THREADS) void detect_kernel(const DetArgs a) {
+// one workgroup per image (blockIdx.x): the same three top-K paths, tie order, NaN handling and NMS on every image of the batch
+__global__ __launch_bounds__(DET_THREADS) void detect_kernel(const DetArgs a0) {
+    DetArgs a = a0;
+    {
+        const size_t b = blockIdx.x, n = (size_t)a0.rows * a0.cols;
+        a.score += b * n;
+        a.loc += b * 4 * n;
+        if (a.lm_heat) a.lm_heat += b * 4 * n;
+        if (a.lm_loc) a.lm_loc += b * 8 * n;
+        a.dets += b * a0.K * a0.dc;
+        a.topk += b * a0.K;
+        a.keep += b * (a0.K + 1);
+        const size_t so = b * (size_t)a0.scratch_stride;
+        a.work = (float*)((char*)a0.work + so);
+        a.order = (int*)((char*)a0.order + so);
+        a.supp = a0.supp + so;
+        if (a.mask) a.mask = (unsigned long long*)((char*)a0.mask + so);
+    }
     __shared__ float red_v[DET_THREADS / 64];
     __shared__ int red_i[DET_THREADS / 64];
     __shared__ int lm_arg[4];
@@ -497,12 +517,18 @@ extern "C" int64_t dbx_detect_scratch_bytes(int32_t rows, int32_t cols, int32_t 
     return (int64_t)rows * cols * 4 + (int64_t)K * 4 + ((int64_t)K + 255) / 256 * 256 + (K <= NMS_LDS_MAX ? (int64_t)K * 128 : 0) + 256;
 }
 
-extern "C" int dbx_detect(const float* score, const float* loc, const float* lm_heat, const float* lm_loc, int32_t rows,
-                          int32_t cols, int32_t K, double nms_thresh, double* dets, int32_t det_cols, int64_t* topk_idx,
-                          int32_t* keep, void* scratch, void* stream) {
-    DBX_REQUIRE(score && loc && dets && topk_idx && keep && scratch, "detect: null argument");
-    DBX_REQUIRE(K > 0 && K <= rows * cols, "detect: K=%d out of range", K);
-    DBX_REQUIRE(det_cols == 5 || (det_cols == 13 && (lm_heat || lm_loc)), "detect: det_cols must be 5, or 13 with landmark maps");
+// one image's slice of the batched scratch: the single-image layout rounded up to 256 B
+static int64_t detect_slice_bytes(int32_t rows, int32_t cols, int32_t K) {
+    return (dbx_detect_scratch_bytes(rows, cols, K) + 255) / 256 * 256;
+}
+
+extern "C" int64_t dbx_detect_batch_scratch_bytes(int32_t batch, int32_t rows, int32_t cols, int32_t K) {
+    return (int64_t)batch * detect_slice_bytes(rows, cols, K);
+}
+
+static int detect_launch(const float* score, const float* loc, const float* lm_heat, const float* lm_loc, int32_t batch, int32_t rows,
+                         int32_t cols, int32_t K, double nms_thresh, double* dets, int32_t det_cols, int64_t* topk_idx, int32_t* keep,
+                         void* scratch, void* stream) {
     DetArgs a;
     a.score = score; a.loc = loc; a.lm_heat = lm_heat; a.lm_loc = lm_loc;
     a.rows = rows; a.cols = cols; a.K = K; a.dc = det_cols; a.thresh = nms_thresh;
@@ -513,9 +539,30 @@ extern "C" int dbx_detect(const float* score, const float* loc, const float* lm_
     a.supp = (unsigned char*)s; s += ((size_t)K + 255) / 256 * 256;
     s = (char*)(((size_t)s + 7) & ~(size_t)7);                          // (inside the 256 spare bytes)
     a.mask = K <= NMS_LDS_MAX ? (unsigned long long*)s : nullptr;
-    hipLaunchKernelGGL(detect_kernel, dim3(1), dim3(DET_THREADS), 0, (hipStream_t)stream, a);
+    a.scratch_stride = detect_slice_bytes(rows, cols, K);
+    hipLaunchKernelGGL(detect_kernel, dim3(batch), dim3(DET_THREADS), 0, (hipStream_t)stream, a);
     DBX_LAUNCH_CHECK();
     return DBX_OK;
+}
+
+extern "C" int dbx_detect(const float* score, const float* loc, const float* lm_heat, const float* lm_loc, int32_t rows,
+                          int32_t cols, int32_t K, double nms_thresh, double* dets, int32_t det_cols, int64_t* topk_idx,
+                          int32_t* keep, void* scratch, void* stream) {
+    DBX_REQUIRE(score && loc && dets && topk_idx && keep && scratch, "detect: null argument");
+    DBX_REQUIRE(K > 0 && K <= rows * cols, "detect: K=%d out of range", K);
+    DBX_REQUIRE(det_cols == 5 || (det_cols == 13 && (lm_heat || lm_loc)), "detect: det_cols must be 5, or 13 with landmark maps");
+    return detect_launch(score, loc, lm_heat, lm_loc, 1, rows, cols, K, nms_thresh, dets, det_cols, topk_idx, keep, scratch, stream);
+}
+
+extern "C" int dbx_detect_batch(const float* score, const float* loc, const float* lm_heat, const float* lm_loc, int32_t batch,
+                                int32_t rows, int32_t cols, int32_t K, double nms_thresh, double* dets, int32_t det_cols,
+                                int64_t* topk_idx, int32_t* keep, void* scratch, void* stream) {
+    DBX_REQUIRE(score && loc && dets && topk_idx && keep && scratch, "detect_batch: null argument");
+    DBX_REQUIRE(batch > 0, "detect_batch: batch=%d must be positive", batch);
+    DBX_REQUIRE(rows > 0 && cols > 0 && (int64_t)rows * cols <= 0x7fffffff, "detect_batch: bad map size %d x %d", rows, cols);
+    DBX_REQUIRE(K > 0 && K <= rows * cols, "detect_batch: K=%d out of range", K);
+    DBX_REQUIRE(det_cols == 5 || (det_cols == 13 && (lm_heat || lm_loc)), "detect_batch: det_cols must be 5, or 13 with landmark maps");
+    return detect_launch(score, loc, lm_heat, lm_loc, batch, rows, cols, K, nms_thresh, dets, det_cols, topk_idx, keep, scratch, stream);
 }
 
 __global__ __launch_bounds__(DET_THREADS) void nms_kernel(const double* dets, int n, int dc, double thresh, int* keep, int* order,

@@ -61,21 +61,109 @@ def NMS(dets, nms_thresh=0.4):
     return [int(v) for v in k[1:1 + int(k[0])]]
 
 
+def _run_batch(score_map, loc_map, K, lm_heat=None, lm_loc=None, nms_thresh=0.4):
+    """dbx_detect_batch over [B,C,rows,cols] maps: dets [B,K,5|13] float64, topk [B,K] int64, keep [B,K+1] int32 (device)."""
+    B, _, rows, cols = score_map.shape
+    assert score_map.size(1) == 1 and loc_map.size() == torch.Size([B, 4, rows, cols])
+    if lm_heat is not None:
+        assert lm_heat.size() == torch.Size([B, 4, rows, cols])
+    if lm_loc is not None:
+        assert lm_loc.size() == torch.Size([B, 8, rows, cols])
+    dev = score_map.device if score_map.is_cuda else torch.device('cuda')
+
+    def f(t):
+        return None if t is None else t.detach().to(dev, torch.float32).contiguous()
+    s, l, hm, ll = f(score_map), f(loc_map), f(lm_heat), f(lm_loc)
+    dc = 5 if (hm is None and ll is None) else 13
+    dets = torch.empty((B, K, dc), dtype=torch.float64, device=dev)
+    topk = torch.empty((B, K), dtype=torch.int64, device=dev)
+    keep = torch.empty((B, K + 1), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    scratch = torch.empty(L.dbx_detect_batch_scratch_bytes(B, rows, cols, K), dtype=torch.uint8, device=dev)
+    check(L.dbx_detect_batch(ptr(s), ptr(l), ptr(hm), ptr(ll), B, rows, cols, K, float(nms_thresh), ptr(dets), dc, ptr(topk),
+                             ptr(keep), ptr(scratch), stream_ptr()))
+    return dets, topk, keep
+
+
 _MAX_GRAPHS = 8
+
+
+def _maps(kind, outs):
+    """(score, loc, lm_heat, lm_loc) the decode ranks and reads per network: the refined score for the landmark nets
+    (DenseBox.py:3626-3643, :3709-3726)."""
+    if kind == 'DenseBox':
+        return outs[0], outs[1], None, None
+    if kind == 'DenseBoxLM':
+        return outs[3], outs[1], outs[2], None
+    return outs[1], outs[2], outs[3], outs[4]
 
 
 def _detect_eager(net, image, K, nms_thresh):
     M, N = image.size(2), image.size(3)
     with torch.no_grad():
         outs = net(image)
-    kind = net.KIND
-    if kind == 'DenseBox':
-        dets, _, keep = _run(outs[0], outs[1], M, N, K, nms_thresh=nms_thresh)
-    elif kind == 'DenseBoxLM':
-        dets, _, keep = _run(outs[3], outs[1], M, N, K, lm_heat=outs[2], nms_thresh=nms_thresh)
-    else:
-        dets, _, keep = _run(outs[1], outs[2], M, N, K, lm_heat=outs[3], lm_loc=outs[4], nms_thresh=nms_thresh)
+    s, l, hm, ll = _maps(net.KIND, outs)
+    dets, _, keep = _run(s, l, M, N, K, lm_heat=hm, lm_loc=ll, nms_thresh=nms_thresh)
     return dets, keep
+
+
+def _detect_batch_eager(net, images, K, nms_thresh):
+    with torch.no_grad():
+        outs = net(images)
+    s, l, hm, ll = _maps(net.KIND, outs)
+    dets, _, keep = _run_batch(s, l, K, lm_heat=hm, lm_loc=ll, nms_thresh=nms_thresh)
+    return dets, keep
+
+
+def _graph_replay(net, tag, image, K, nms_thresh, eager):
+    """Replays (capturing on the first call) one hipGraph of eager(net, image, K, nms_thresh) -> (dets, keep) device tensors
+    and returns the two results in pinned host tensors, valid until the next call.  One cache per network, shared by
+    detect() and detect_batch(): keyed by (tag, input shape, input dtype, K, threshold, compute dtype), re-captured when the
+    weight signature changes, at most _MAX_GRAPHS entries (LRU)."""
+    import collections
+    cache = net.__dict__.setdefault('_detect_graphs', collections.OrderedDict())
+    # weight signature: versions + storage addresses of every parameter (a replay reads the packed copies made at capture).
+    # Read straight from the sub-modules' parameter dicts (sees in-place updates, .to()/.half() and replaced Parameter
+    # objects; 12 us instead of the 75 us Module.parameters() spends walking the tree); the list of dicts itself is
+    # rebuilt every 64 calls in case a whole sub-module was swapped.
+    # A replaced sub-module (net.conv6_3_det = nn.Conv2d(...)) changes the DIRECT children's identities: their ids are part
+    # of the signature (one dict walk), and the cached list is rebuilt whenever they differ.
+    kids = tuple(id(m) for m in net._modules.values())
+    pd = net.__dict__.get('_detect_pdicts')
+    if pd is None or pd[0] <= 0 or pd[2] != kids:
+        pd = [64, [m._parameters for m in net.modules() if m._parameters], kids]
+        net.__dict__['_detect_pdicts'] = pd
+    pd[0] -= 1
+    sig = (kids,) + tuple([(p._version, p.data_ptr()) for d in pd[1] for p in d.values() if p is not None])
+    key = (tag, tuple(image.shape), image.dtype, K, float(nms_thresh), net.resolved_dtype(False))
+    ent = cache.get(key)
+    if ent is None or ent[0] != sig:
+        static_in = image.clone()
+        for _ in range(2):                       # warm: workspace plan, packed weights, scratch buffers, kernel attributes
+            wd, wk = eager(net, static_in, K, nms_thresh)
+        h_dets = torch.empty(wd.shape, dtype=wd.dtype).pin_memory()        # (pinned allocation is not capturable)
+        h_keep = torch.empty(wk.shape, dtype=wk.dtype).pin_memory()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            dets, keep = eager(net, static_in, K, nms_thresh)
+            # the two result copies are graph nodes too (pinned destinations): one replay + one stream sync per call
+            # instead of two blocking .cpu() calls with their launch round trips (~60 us of idle GPU per call)
+            h_dets.copy_(dets, non_blocking=True)
+            h_keep.copy_(keep, non_blocking=True)
+        # The captured kernels hold RAW pointers into the engine's workspace plan and packed / folded weight buffers.  The
+        # engine keeps one plan and re-creates its weight caches when the dtype or mode flips, so the entry pins every
+        # tensor it captured: a later forward at another shape (or a train-mode step) cannot free what a replay reads.
+        ent = (sig, g, static_in, dets, keep, net._engine.captured_refs(), h_dets, h_keep)
+        cache[key] = ent
+        while len(cache) > _MAX_GRAPHS:            # bounded: one graph + private pool + pinned workspace per shape
+            cache.popitem(last=False)
+    cache.move_to_end(key)
+    _, g, static_in, dets, keep, _refs, h_dets, h_keep = ent
+    static_in.copy_(image)
+    g.replay()
+    torch.cuda.current_stream().synchronize()
+    return h_dets, h_keep
 
 
 def detect(net, image, K=10, nms_thresh=0.4):
@@ -91,50 +179,77 @@ def detect(net, image, K=10, nms_thresh=0.4):
     if not use_graph:
         dets, keep = _detect_eager(net, image, K, nms_thresh)
     else:
-        import collections
-        cache = net.__dict__.setdefault('_detect_graphs', collections.OrderedDict())
-        # weight signature: versions + storage addresses of every parameter (a replay reads the packed copies made at capture).
-        # Read straight from the sub-modules' parameter dicts (sees in-place updates, .to()/.half() and replaced Parameter
-        # objects; 12 us instead of the 75 us Module.parameters() spends walking the tree); the list of dicts itself is
-        # rebuilt every 64 calls in case a whole sub-module was swapped.
-        # A replaced sub-module (net.conv6_3_det = nn.Conv2d(...)) changes the DIRECT children's identities: their ids are part
-        # of the signature (one dict walk), and the cached list is rebuilt whenever they differ.
-        kids = tuple(id(m) for m in net._modules.values())
-        pd = net.__dict__.get('_detect_pdicts')
-        if pd is None or pd[0] <= 0 or pd[2] != kids:
-            pd = [64, [m._parameters for m in net.modules() if m._parameters], kids]
-            net.__dict__['_detect_pdicts'] = pd
-        pd[0] -= 1
-        sig = (kids,) + tuple([(p._version, p.data_ptr()) for d in pd[1] for p in d.values() if p is not None])
-        key = (tuple(image.shape), image.dtype, K, float(nms_thresh), net.resolved_dtype(False))
-        ent = cache.get(key)
-        if ent is None or ent[0] != sig:
-            static_in = image.clone()
-            for _ in range(2):                       # warm: workspace plan, packed weights, scratch buffers, kernel attributes
-                wd, wk = _detect_eager(net, static_in, K, nms_thresh)
-            h_dets = torch.empty(wd.shape, dtype=wd.dtype).pin_memory()        # (pinned allocation is not capturable)
-            h_keep = torch.empty(wk.shape, dtype=wk.dtype).pin_memory()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                dets, keep = _detect_eager(net, static_in, K, nms_thresh)
-                # the two result copies are graph nodes too (pinned destinations): one replay + one stream sync per image
-                # instead of two blocking .cpu() calls with their launch round trips (~60 us of idle GPU per image)
-                h_dets.copy_(dets, non_blocking=True)
-                h_keep.copy_(keep, non_blocking=True)
-            # The captured kernels hold RAW pointers into the engine's workspace plan and packed / folded weight buffers.  The
-            # engine keeps one plan and re-creates its weight caches when the dtype or mode flips, so the entry pins every
-            # tensor it captured: a later forward at another shape (or a train-mode step) cannot free what a replay reads.
-            ent = (sig, g, static_in, dets, keep, net._engine.captured_refs(), h_dets, h_keep)
-            cache[key] = ent
-            while len(cache) > _MAX_GRAPHS:            # bounded: one graph + private pool + pinned workspace per shape
-                cache.popitem(last=False)
-        cache.move_to_end(key)
-        _, g, static_in, dets, keep, _refs, h_dets, h_keep = ent
-        static_in.copy_(image)
-        g.replay()
-        torch.cuda.current_stream().synchronize()
+        h_dets, h_keep = _graph_replay(net, 'detect', image, K, nms_thresh, _detect_eager)
         k = h_keep.numpy()
         return h_dets.numpy().copy(), [int(v) for v in k[1:1 + int(k[0])]]
     k = keep.cpu().numpy()
     return dets.cpu().numpy(), [int(v) for v in k[1:1 + int(k[0])]]
+
+
+def _batch_of(x, what):
+    """A 4-d network input from one tensor of `what`: float [B,3,H,W] or uint8 [B,H,W,3]."""
+    if not torch.is_tensor(x):
+        raise RuntimeError('detect_batch: %s must be a tensor, got %s' % (what, type(x).__name__))
+    if x.dtype == torch.uint8:
+        if x.dim() != 4 or x.size(3) != 3:
+            raise RuntimeError('detect_batch: uint8 %s must be [B,H,W,3] (HWC, RGB), got %s' % (what, list(x.shape)))
+    elif not x.is_floating_point() or x.dim() != 4 or x.size(1) != 3:
+        raise RuntimeError('detect_batch: %s must be float [B,3,H,W] or uint8 [B,H,W,3], got %s %s' % (what, x.dtype, list(x.shape)))
+    return x
+
+
+def _detect_chunk(net, x, K, nms_thresh):
+    import os
+    x = (x if x.is_cuda else x.cuda()).contiguous()
+    if not net.training and os.environ.get('DBX_GRAPH', '1') != '0':
+        h_dets, h_keep = _graph_replay(net, 'batch', x, K, nms_thresh, _detect_batch_eager)
+    else:
+        dets, keep = _detect_batch_eager(net, x, K, nms_thresh)
+        h_dets, h_keep = dets.cpu(), keep.cpu()
+    d, k = h_dets.numpy(), h_keep.numpy()
+    return [(d[b].copy(), [int(v) for v in k[b, 1:1 + int(k[b, 0])]]) for b in range(d.shape[0])]
+
+
+def detect_batch(net, images, K=10, nms_thresh=0.4, max_batch=32):
+    """detect() over many images: one forward and ONE decode + NMS launch (a workgroup per image, dbx_detect_batch) per chunk
+    of at most `max_batch` images.  Returns a list with detect()'s (dets[K, 5|13] float64 ndarray, keep list) per image, in
+    input order.
+
+    images: a float [B,3,H,W] or uint8 [B,H,W,3] (RGB, normalised on the device) tensor on the CPU or the GPU, or a list /
+    tuple of single images -- float [3,H,W] or [1,3,H,W], uint8 [H,W,3] or [1,H,W,3] -- of any sizes (the reference test()
+    loop's directory walk).  List images are grouped by (shape, dtype) and never padded into one forward: padding would change
+    the border activations after the first pooling and the bilinear up-sampling.  Eval mode replays a hipGraph per (batch
+    shape, dtype, K, threshold, compute dtype) from the cache detect() uses; train mode and DBX_GRAPH=0 run eagerly."""
+    if max_batch < 1:
+        raise RuntimeError('detect_batch: max_batch=%d must be positive' % max_batch)
+    if not isinstance(images, (list, tuple)):
+        x = _batch_of(images, 'images')
+        if x.size(0) == 0:
+            raise RuntimeError('detect_batch: empty batch')
+        out = []
+        for i in range(0, x.size(0), max_batch):
+            out += _detect_chunk(net, x[i:i + max_batch], K, nms_thresh)
+        return out
+    if len(images) == 0:
+        raise RuntimeError('detect_batch: empty list of images')
+    one = []
+    for i, im in enumerate(images):
+        if torch.is_tensor(im) and im.dim() == 3:
+            im = im.unsqueeze(0)
+        one.append(_batch_of(im, 'images[%d]' % i))
+        if one[-1].size(0) != 1:
+            raise RuntimeError('detect_batch: images[%d] holds %d images; a list takes single images' % (i, one[-1].size(0)))
+    if len({im.dtype == torch.uint8 for im in one}) > 1:
+        raise RuntimeError('detect_batch: the list mixes uint8 [H,W,3] and float [3,H,W] images')
+    groups = {}
+    for i, im in enumerate(one):
+        groups.setdefault((tuple(im.shape), im.dtype), []).append(i)
+    out = [None] * len(one)
+    for idx in groups.values():
+        for c in range(0, len(idx), max_batch):
+            part = idx[c:c + max_batch]
+            dev = next((one[i].device for i in part if one[i].is_cuda), torch.device('cuda'))
+            res = _detect_chunk(net, torch.cat([one[i].to(dev) for i in part]), K, nms_thresh)
+            for i, r in zip(part, res):
+                out[i] = r
+    return out

@@ -123,6 +123,12 @@ class _DenseBoxBase(nn.Module):
         from .decode import detect
         return detect(self, image, K, nms_thresh)
 
+    def detect_batch(self, images, K=10, nms_thresh=0.4, max_batch=32):
+        """detect() over a batch tensor or a list of images: one forward + one decode / NMS launch per chunk of <= max_batch
+        same-shape images; a list of (dets, keep) in input order (densebox_amd.decode.detect_batch)."""
+        from .decode import detect_batch
+        return detect_batch(self, images, K, nms_thresh, max_batch)
+
 
 class DenseBox(_DenseBoxBase):
     KIND = 'DenseBox'

@@ -46,8 +46,9 @@ const char* dbx_last_error(void);
  *   6  (round 5) dbx_conv_plan may name DBX_K_P8 (the 8-phase kernel: plain packed weights); dbx_heads_forward_fusable returns WHICH kernel
  *      takes the fused heads forward (1 = ws / fragment-order weights as before, 2 = 8-phase / plain weights + plain second-weight image)
  *   7  (round 6) additions only: dbx_grad_guard, dbx_sgd_step_guarded, dbx_sgd_pack_step_guarded (f16 overflow guard), dbx_conv_wgrad_pool_dz; the heads-gen
- *      entry points accept DBX_F32 (reference instantiations for the parity suite) */
-#define DBX_ABI_VERSION 7
+ *      entry points accept DBX_F32 (reference instantiations for the parity suite)
+ *   8  additions only: dbx_detect_batch, dbx_detect_batch_scratch_bytes (one decode + NMS launch over a batch of images) */
+#define DBX_ABI_VERSION 8
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
 int dbx_device_arch(int device);
@@ -430,6 +431,14 @@ int dbx_detect(const float* score, const float* loc, const float* lm_heat, const
                int32_t rows, int32_t cols, int32_t K, double nms_thresh,
                double* dets, int32_t det_cols, int64_t* topk_idx, int32_t* keep, void* scratch, void* stream);
 int64_t dbx_detect_scratch_bytes(int32_t rows, int32_t cols, int32_t K);
+/* the same over `batch` images in one launch (one workgroup per image): maps contiguous [batch][C][rows][cols] fp32 (C = 1, 4, 4, 8
+ * for score, loc, lm_heat, lm_loc), dets [batch][K][det_cols], topk_idx [batch][K], keep [batch][K+1].  Image b's result is bit for
+ * bit what dbx_detect gives on its own maps.  Scratch: dbx_detect_batch_scratch_bytes, one 256-byte-aligned slice per image of
+ * dbx_detect_scratch_bytes rounded up to 256 bytes.  dbx_detect is this launch with batch = 1. */
+int64_t dbx_detect_batch_scratch_bytes(int32_t batch, int32_t rows, int32_t cols, int32_t K);
+int dbx_detect_batch(const float* score, const float* loc, const float* lm_heat, const float* lm_loc,
+                     int32_t batch, int32_t rows, int32_t cols, int32_t K, double nms_thresh,
+                     double* dets, int32_t det_cols, int64_t* topk_idx, int32_t* keep, void* scratch, void* stream);
 /* scratch: 5*n bytes */
 int dbx_nms(const double* dets, int32_t n, int32_t det_cols, double nms_thresh, int32_t* keep, void* scratch, void* stream);
 
