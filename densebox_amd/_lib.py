@@ -48,6 +48,12 @@ class LossIO(C.Structure):
         'loss', 'mask_cls', 'mask_lm', 'neg_idx', 'lm_neg_idx', 'pos_count')]
 
 
+class WarpJob(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('sh', C.c_int32), ('sw', C.c_int32), ('m9', C.c_double * 9), ('dh', C.c_int32),
+                ('dw', C.c_int32), ('x0', C.c_int32), ('y0', C.c_int32), ('oh', C.c_int32), ('ow', C.c_int32),
+                ('dst_off', C.c_int64)]
+
+
 _VP, _I32, _I64, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 _PV, _PC = C.POINTER(View), C.POINTER(ConvDesc)
 
@@ -93,6 +99,8 @@ SIGNATURES = {
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _VP, _PV, _VP]),
     'dbx_perspective_matrix': (C.c_int, [_VP, _VP, _VP]),
     'dbx_warp_perspective_u8': (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP]),
+    'dbx_warp_batch_workspace_bytes': (_I64, [_I32]),
+    'dbx_warp_perspective_batch_u8': (C.c_int, [C.POINTER(WarpJob), _I32, _I32, _VP, _VP, _VP]),
     'dbx_conv_wgrad_scratch_bytes': (_I64, [_I32, _PV, _PV, _I32, _I32]),
     'dbx_conv_wgrad': (C.c_int, [_I32, _PV, _PV, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _I32, _VP]),
     'dbx_conv_wgrad_slice': (C.c_int, [_I32, _PV, _PV, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP]),
@@ -137,7 +145,7 @@ SIGNATURES = {
     'dbx_nms': (C.c_int, [_VP, _I32, _I32, _D, _VP, _VP, _VP]),
 }
 
-ABI_VERSION = 8          # include/densebox_hip.h DBX_ABI_VERSION this binding was written against
+ABI_VERSION = 9          # include/densebox_hip.h DBX_ABI_VERSION this binding was written against
 _lib = None
 MISSING = []
 

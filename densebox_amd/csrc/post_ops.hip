@@ -4,6 +4,9 @@
 #pragma clang fp contract(off)
 #include "common.hpp"
 
+#include <cmath>
+#include <vector>
+
 // ---------------------------------------------------------------------------------------------- SGD (DenseBox.py:2001-2004)
 // torch.optim.SGD, dampening 0, no Nesterov: g = grad + wd*p; buf = g (first step) | mu*buf + g; p -= lr*buf
 // guard (round 6): dbx_grad_guard leaves step_id in guard[0] when any gradient element of the step is not finite (f16 training keeps its
@@ -617,41 +620,199 @@ extern "C" int dbx_perspective_matrix(const float* src_xy, const float* dst_xy, 
     return DBX_OK;
 }
 
-struct WarpArgs { const unsigned char* src; unsigned char* dst; int sh, sw, c, dh, dw; double im[9]; };
-__global__ void warp_perspective_u8_kernel(const WarpArgs a) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= a.dw || y >= a.dh) return;
-    const double X0 = a.im[0] * x + a.im[1] * y + a.im[2], Y0 = a.im[3] * x + a.im[4] * y + a.im[5];
-    double W = a.im[6] * x + a.im[7] * y + a.im[8];
+// One output pixel of the warp at canvas coordinate (x, y): the inverse map in fp64, the source coordinate rounded to 1/32 pixel,
+// 15-bit bilinear weights, a zero border; channel ch of the result in byte ch.  Both warp kernels call it, so the batched one writes
+// what the single-image one writes, bit for bit (fp contraction is off for the whole file).
+template <typename SrcPtr>
+__device__ __forceinline__ unsigned int warp_px_u8(const double* im, SrcPtr src, int sh, int sw, int c, int x, int y) {
+    const double X0 = im[0] * x + im[1] * y + im[2], Y0 = im[3] * x + im[4] * y + im[5];
+    double W = im[6] * x + im[7] * y + im[8];
     W = W != 0.0 ? 32.0 / W : 0.0;
     const double fX = fmax(-2147483648.0, fmin(2147483647.0, X0 * W)), fY = fmax(-2147483648.0, fmin(2147483647.0, Y0 * W));
     const int X = (int)rint(fX), Y = (int)rint(fY);                          // cvRound: nearest, ties to even
     const int sx = X >> 5, sy = Y >> 5, ax = X & 31, ay = Y & 31;
     const int w00 = (32 - ax) * (32 - ay) * 32, w01 = ax * (32 - ay) * 32, w10 = (32 - ax) * ay * 32, w11 = ax * ay * 32;
-    const bool x0 = sx >= 0 && sx < a.sw, x1 = sx + 1 >= 0 && sx + 1 < a.sw, y0 = sy >= 0 && sy < a.sh, y1 = sy + 1 >= 0 && sy + 1 < a.sh;
-    for (int ch = 0; ch < a.c; ++ch) {
-        const int p00 = (x0 && y0) ? a.src[((size_t)sy * a.sw + sx) * a.c + ch] : 0;
-        const int p01 = (x1 && y0) ? a.src[((size_t)sy * a.sw + sx + 1) * a.c + ch] : 0;
-        const int p10 = (x0 && y1) ? a.src[((size_t)(sy + 1) * a.sw + sx) * a.c + ch] : 0;
-        const int p11 = (x1 && y1) ? a.src[((size_t)(sy + 1) * a.sw + sx + 1) * a.c + ch] : 0;
+    const bool x0 = sx >= 0 && sx < sw, x1 = sx + 1 >= 0 && sx + 1 < sw, y0 = sy >= 0 && sy < sh, y1 = sy + 1 >= 0 && sy + 1 < sh;
+    unsigned int px = 0;
+    for (int ch = 0; ch < c; ++ch) {
+        const int p00 = (x0 && y0) ? src[((size_t)sy * sw + sx) * c + ch] : 0;
+        const int p01 = (x1 && y0) ? src[((size_t)sy * sw + sx + 1) * c + ch] : 0;
+        const int p10 = (x0 && y1) ? src[((size_t)(sy + 1) * sw + sx) * c + ch] : 0;
+        const int p11 = (x1 && y1) ? src[((size_t)(sy + 1) * sw + sx + 1) * c + ch] : 0;
         const int v = (p00 * w00 + p01 * w01 + p10 * w10 + p11 * w11 + (1 << 14)) >> 15;
-        a.dst[((size_t)y * a.dw + x) * a.c + ch] = (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
+        px |= (unsigned int)(v < 0 ? 0 : (v > 255 ? 255 : v)) << (8 * ch);
     }
+    return px;
 }
+
+struct WarpArgs { const unsigned char* src; unsigned char* dst; int sh, sw, c, dh, dw; double im[9]; };
+__global__ void warp_perspective_u8_kernel(const WarpArgs a) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= a.dw || y >= a.dh) return;
+    const unsigned int px = warp_px_u8(a.im, a.src, a.sh, a.sw, a.c, x, y);
+    for (int ch = 0; ch < a.c; ++ch) a.dst[((size_t)y * a.dw + x) * a.c + ch] = (unsigned char)(px >> (8 * ch));
+}
+
+// dst -> src map: the inverse of the 3x3 src -> dst map m, cofactor form in double.  False when the determinant is zero.
+static bool warp_inverse(const double* m, double* im) {
+    const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
+    if (det == 0.0) return false;
+    const double d = 1.0 / det;
+    im[0] = (m[4] * m[8] - m[5] * m[7]) * d; im[1] = (m[2] * m[7] - m[1] * m[8]) * d; im[2] = (m[1] * m[5] - m[2] * m[4]) * d;
+    im[3] = (m[5] * m[6] - m[3] * m[8]) * d; im[4] = (m[0] * m[8] - m[2] * m[6]) * d; im[5] = (m[2] * m[3] - m[0] * m[5]) * d;
+    im[6] = (m[3] * m[7] - m[4] * m[6]) * d; im[7] = (m[1] * m[6] - m[0] * m[7]) * d; im[8] = (m[0] * m[4] - m[1] * m[3]) * d;
+    return true;
+}
+
 extern "C" int dbx_warp_perspective_u8(const uint8_t* src, int32_t sh, int32_t sw, int32_t c, const double* m9, uint8_t* dst,
                                        int32_t dh, int32_t dw, void* stream) {
     DBX_REQUIRE(src && dst && m9 && sh > 0 && sw > 0 && dh > 0 && dw > 0 && c >= 1 && c <= 4, "warp_perspective: bad arguments");
-    // inverse of the 3x3 map (dst -> src), cofactor form in double
-    const double* m = m9;
-    const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-    DBX_REQUIRE(det != 0.0, "warp_perspective: singular matrix");
-    const double d = 1.0 / det;
     WarpArgs a;
+    DBX_REQUIRE(warp_inverse(m9, a.im), "warp_perspective: singular matrix");
     a.src = src; a.dst = dst; a.sh = sh; a.sw = sw; a.c = c; a.dh = dh; a.dw = dw;
-    a.im[0] = (m[4] * m[8] - m[5] * m[7]) * d; a.im[1] = (m[2] * m[7] - m[1] * m[8]) * d; a.im[2] = (m[1] * m[5] - m[2] * m[4]) * d;
-    a.im[3] = (m[5] * m[6] - m[3] * m[8]) * d; a.im[4] = (m[0] * m[8] - m[2] * m[6]) * d; a.im[5] = (m[2] * m[3] - m[0] * m[5]) * d;
-    a.im[6] = (m[3] * m[7] - m[4] * m[6]) * d; a.im[7] = (m[1] * m[6] - m[0] * m[7]) * d; a.im[8] = (m[0] * m[4] - m[1] * m[3]) * d;
     hipLaunchKernelGGL(warp_perspective_u8_kernel, dim3((dw + 255) / 256, dh), dim3(256), 0, (hipStream_t)stream, a);
+    DBX_LAUNCH_CHECK();
+    return DBX_OK;
+}
+
+// ---- batched warp: every plate of a batch in one launch (dbx_warp_perspective_batch_u8)
+// A job's output window [oh][ow][c] is one contiguous byte range, so the kernel walks it as a flat list of oh*ow pixels (wrapping from
+// one window row to the next).  Each wave owns a segment of WARP_SEG consecutive pixels.  Pass 1: in each of WARP_PPT steps the 64
+// lanes make 64 CONSECUTIVE pixels -- the neighbour gathers of a wave instruction cover a narrow span of the source, as in the
+// single-image kernel -- and put their c bytes into the wave's slice of LDS.  Pass 2: each lane stores 16-byte words of the segment
+// (64 consecutive words per wave instruction) when the job's output is 16-byte aligned, dwords when it is 4-byte aligned, bytes
+// otherwise and for the job's last partial word.  Source and destination go through global-address-space pointers (global_load /
+// global_store, not flat).  A tile is one workgroup's WARP_THREADS / 64 segments; tile0[j] is the first tile of job j (a prefix of
+// the per-job tile counts), and each workgroup finds its job by a binary search of tile0.
+#define WARP_THREADS 256
+#define WARP_PPT 8
+#define WARP_SEG (64 * WARP_PPT)
+typedef const __attribute__((address_space(1))) unsigned char* warp_gsrc_t;
+typedef __attribute__((address_space(1))) unsigned char* warp_gdst_t;
+typedef __attribute__((address_space(1))) u32x4* warp_gdst4_t;
+typedef __attribute__((address_space(1))) unsigned int* warp_gdst1_t;
+struct WarpJobDev {                     // device record of one job (128 bytes)
+    const unsigned char* src;
+    unsigned char* dst;                 // dst + dst_off
+    double im[9];                       // canvas -> source map
+    long long npix;                     // oh * ow
+    int sh, sw, x0, y0, ow, pad[3];
+};
+static_assert(sizeof(WarpJobDev) == 128, "WarpJobDev layout");
+
+template <int C>
+__global__ __launch_bounds__(WARP_THREADS) void warp_perspective_batch_u8_kernel(const WarpJobDev* __restrict__ jobs,
+                                                                                  const int* __restrict__ tile0, int njobs) {
+    __shared__ __attribute__((aligned(16))) unsigned char seg[WARP_THREADS / 64][WARP_SEG * C];
+    const int t = blockIdx.x;
+    int lo = 0, hi = njobs - 1;                        // the last job whose first tile is <= t (jobs without tiles never match)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tile0[mid] <= t) lo = mid; else hi = mid - 1;
+    }
+    const WarpJobDev* J = jobs + lo;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long npix = J->npix;
+    const long long s0 = ((long long)(t - tile0[lo]) * (WARP_THREADS / 64) + wave) * WARP_SEG;   // first pixel of the wave's segment
+    const int nseg = s0 >= npix ? 0 : (npix - s0 < WARP_SEG ? (int)(npix - s0) : WARP_SEG);       // its pixels (wave-uniform)
+    unsigned char* L = seg[wave];
+    if (nseg > 0) {
+        double im[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) im[i] = J->im[i];
+        const warp_gsrc_t src = (warp_gsrc_t)J->src;
+        const int sh = J->sh, sw = J->sw, ow = J->ow, x0 = J->x0, y0 = J->y0;
+        const long long p = s0 + lane;
+        int y = (int)(p / ow), x = (int)(p - (long long)y * ow);
+#pragma unroll
+        for (int i = 0; i < WARP_PPT; ++i) {
+            const int q = i * 64 + lane;
+            if (q < nseg) {
+                const unsigned int px = warp_px_u8(im, src, sh, sw, C, x0 + x, y0 + y);
+                if (C == 4) {
+                    reinterpret_cast<unsigned int*>(L)[q] = px;
+                } else {
+#pragma unroll
+                    for (int ch = 0; ch < C; ++ch) L[q * C + ch] = (unsigned char)(px >> (8 * ch));
+                }
+            }
+            x += 64;                                   // the lane's next pixel is 64 further on
+            if (x >= ow) { y += x / ow; x %= ow; }
+        }
+    }
+    __syncthreads();
+    if (nseg == 0) return;
+    const warp_gdst_t d = (warp_gdst_t)(J->dst + s0 * C);
+    const int nb = nseg * C;
+    const size_t al = (size_t)d;
+    for (int k = lane; 16 * k < nb; k += 64) {
+        const int b0 = 16 * k;
+        if (b0 + 16 <= nb && al % 16 == 0) {
+            reinterpret_cast<warp_gdst4_t>(d)[k] = reinterpret_cast<const u32x4*>(L)[k];
+        } else if (b0 + 16 <= nb && al % 4 == 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) reinterpret_cast<warp_gdst1_t>(d)[4 * k + j] = reinterpret_cast<const unsigned int*>(L)[4 * k + j];
+        } else {
+            for (int j = b0; j < nb && j < b0 + 16; ++j) d[j] = L[j];
+        }
+    }
+}
+
+static int64_t warp_tile0_offset(int32_t njobs) { return (int64_t)njobs * (int64_t)sizeof(WarpJobDev); }
+
+extern "C" int64_t dbx_warp_batch_workspace_bytes(int32_t njobs) {
+    if (njobs < 0) return -1;
+    return (warp_tile0_offset(njobs) + 4 * ((int64_t)njobs + 1) + 255) / 256 * 256;
+}
+
+extern "C" int dbx_warp_perspective_batch_u8(const dbx_warp_job* jobs, int32_t njobs, int32_t c, uint8_t* dst, void* workspace,
+                                             void* stream) {
+    DBX_REQUIRE(njobs >= 0, "warp_perspective_batch: njobs=%d is negative", njobs);
+    DBX_REQUIRE(c >= 1 && c <= 4, "warp_perspective_batch: c=%d must be 1..4", c);
+    if (njobs == 0) return DBX_OK;
+    DBX_REQUIRE(jobs && dst && workspace, "warp_perspective_batch: null argument");
+    std::vector<WarpJobDev> rec(njobs);
+    std::vector<int> tile0(njobs + 1);
+    constexpr long long tile = (long long)WARP_THREADS * WARP_PPT;        // pixels per workgroup
+    long long tiles = 0;
+    for (int j = 0; j < njobs; ++j) {
+        const dbx_warp_job& g = jobs[j];
+        DBX_REQUIRE(g.src, "warp_perspective_batch: job %d has a null source", j);
+        DBX_REQUIRE(g.sh > 0 && g.sw > 0 && g.dh > 0 && g.dw > 0 && g.oh > 0 && g.ow > 0,
+                    "warp_perspective_batch: job %d has a non-positive size (source %d x %d, canvas %d x %d, window %d x %d)", j, g.sh,
+                    g.sw, g.dh, g.dw, g.oh, g.ow);
+        DBX_REQUIRE(g.x0 >= 0 && g.y0 >= 0 && (int64_t)g.x0 + g.ow <= g.dw && (int64_t)g.y0 + g.oh <= g.dh,
+                    "warp_perspective_batch: job %d window (%d, %d) + %d x %d lies outside its %d x %d canvas", j, g.x0, g.y0, g.ow, g.oh,
+                    g.dw, g.dh);
+        DBX_REQUIRE(g.dst_off >= 0, "warp_perspective_batch: job %d has a negative dst_off", j);
+        WarpJobDev& r = rec[j];
+        bool finite = true;
+        for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(g.m9[i]);
+        DBX_REQUIRE(finite, "warp_perspective_batch: job %d has a non-finite matrix", j);
+        DBX_REQUIRE(warp_inverse(g.m9, r.im), "warp_perspective_batch: job %d has a singular matrix", j);
+        r.src = g.src; r.dst = dst + g.dst_off; r.npix = (long long)g.oh * g.ow;
+        r.sh = g.sh; r.sw = g.sw; r.x0 = g.x0; r.y0 = g.y0; r.ow = g.ow; r.pad[0] = r.pad[1] = r.pad[2] = 0;
+        tile0[j] = (int)tiles;
+        tiles += (r.npix + tile - 1) / tile;
+        // one workgroup per tile, and a grid holds at most 2^32 - 1 work-items per dimension
+        DBX_REQUIRE(tiles <= 0xffffffffLL / WARP_THREADS, "warp_perspective_batch: more than %lld tiles of %lld pixels", 0xffffffffLL / WARP_THREADS,
+                    tile);
+    }
+    tile0[njobs] = (int)tiles;
+    // pageable host source: the copy has read both vectors when it returns, so they may go out of scope (and `jobs` be reused)
+    unsigned char* ws = (unsigned char*)workspace;
+    DBX_HIP(hipMemcpyAsync(ws, rec.data(), sizeof(WarpJobDev) * njobs, hipMemcpyHostToDevice, (hipStream_t)stream));
+    DBX_HIP(hipMemcpyAsync(ws + warp_tile0_offset(njobs), tile0.data(), sizeof(int) * (njobs + 1), hipMemcpyHostToDevice,
+                           (hipStream_t)stream));
+    const WarpJobDev* dj = (const WarpJobDev*)ws;
+    const int* dt = (const int*)(ws + warp_tile0_offset(njobs));
+    const dim3 grid((unsigned)tiles), block(WARP_THREADS);
+    switch (c) {
+        case 1: hipLaunchKernelGGL(warp_perspective_batch_u8_kernel<1>, grid, block, 0, (hipStream_t)stream, dj, dt, njobs); break;
+        case 2: hipLaunchKernelGGL(warp_perspective_batch_u8_kernel<2>, grid, block, 0, (hipStream_t)stream, dj, dt, njobs); break;
+        case 3: hipLaunchKernelGGL(warp_perspective_batch_u8_kernel<3>, grid, block, 0, (hipStream_t)stream, dj, dt, njobs); break;
+        default: hipLaunchKernelGGL(warp_perspective_batch_u8_kernel<4>, grid, block, 0, (hipStream_t)stream, dj, dt, njobs); break;
+    }
     DBX_LAUNCH_CHECK();
     return DBX_OK;
 }

@@ -253,3 +253,33 @@ def detect_batch(net, images, K=10, nms_thresh=0.4, max_batch=32):
             for i, r in zip(part, res):
                 out[i] = r
     return out
+
+
+def detect_plates(net, images, K=10, nms_thresh=0.4, max_batch=32, *, region):
+    """detect_batch, then perspective_transform (DenseBox.py:3446-3481, as viz_result calls it at :3546-3553) on every kept
+    detection: the frames go to the device once, and ONE dbx_warp_perspective_batch_u8 launch rectifies the plates of all chunks.
+
+    images: uint8 frames only -- a [B,H,W,3] tensor or a list of [H,W,3] images (numpy arrays or tensors) of any sizes; those are
+    the pixels the reference warps.  net: DenseBoxLM or DenseBoxLMLOC (rows with landmarks).  region: 'canvas' (the reference's
+    whole 1.5x image) or 'plate' (its window over the plate rectangle), as for rectify.perspective_transform_batch.
+
+    Returns, per image in input order, (dets, keep, plates): detect_batch's (dets, keep) unchanged, and plates[j] the uint8
+    [oh, ow, 3] rectification of row keep[j], whose quad is (det[5:7], det[7:9], det[9:11], det[11:13]) = (left-up, right-up,
+    right-down, left-down), or None where rectify.perspective_transform_batch gives None.  Plates are of the kind of their frame
+    (CUDA tensors are views into one device arena).  detect_batch replays its cached hipGraphs in eval mode; the rectification
+    launch is NOT captured, because its size depends on the detections."""
+    from . import rectify
+    rectify.check_region('detect_plates', region)
+    if net.KIND == 'DenseBox':
+        raise RuntimeError('detect_plates: DenseBox rows have no landmarks to rectify; use DenseBoxLM or DenseBoxLMLOC')
+    host, kinds = rectify.host_images('detect_plates', images, 3)
+    if torch.is_tensor(images):                    # one upload of the batch; the forward and the warp read the same device copy
+        x = (images if images.is_cuda else images.cuda()).contiguous()
+        dev = list(x.unbind(0))
+        res = detect_batch(net, x, K, nms_thresh, max_batch)
+    else:
+        dev = rectify.to_device(images, host)
+        res = detect_batch(net, dev, K, nms_thresh, max_batch)
+    quads = [[[[d[k, 5], d[k, 6]], [d[k, 7], d[k, 8]], [d[k, 9], d[k, 10]], [d[k, 11], d[k, 12]]] for k in keep] for d, keep in res]
+    plates = rectify._warp_batch(dev, kinds, quads, region)
+    return [(d, keep, p) for (d, keep), p in zip(res, plates)]

@@ -129,6 +129,12 @@ class _DenseBoxBase(nn.Module):
         from .decode import detect_batch
         return detect_batch(self, images, K, nms_thresh, max_batch)
 
+    def detect_plates(self, images, K=10, nms_thresh=0.4, max_batch=32, *, region):
+        """detect_batch() on uint8 frames, then every kept detection's plate rectified in one launch: a list of (dets, keep, plates)
+        in input order (densebox_amd.decode.detect_plates)."""
+        from .decode import detect_plates
+        return detect_plates(self, images, K, nms_thresh, max_batch, region=region)
+
 
 class DenseBox(_DenseBoxBase):
     KIND = 'DenseBox'

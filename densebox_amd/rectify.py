@@ -3,6 +3,7 @@
 delegates to cv2.getPerspectiveTransform / cv2.warpPerspective.  OpenCV is not part of the reference tree: the kernels
 follow its published algorithm (see csrc/post_ops.hip); parity with OpenCV itself is unpinned."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -50,3 +51,159 @@ def perspective_transform(img, src_pts):
     M = get_perspective_matrix(src_pts, dst_rectangle(src_pts))
     h, w = img.shape[0], img.shape[1]
     return warp_perspective(img, M, (int(w * 1.5 + 0.5), int(h * 1.5 + 0.5)))
+
+
+_REGIONS = ('canvas', 'plate')
+_ALIGN = 64                    # byte alignment of every job's output in the arena (the kernel stores 16-byte words when aligned)
+
+
+def check_region(who, region):
+    if region not in _REGIONS:
+        raise RuntimeError("%s: region must be 'canvas' or 'plate', got %r" % (who, region))
+
+
+def canvas_size(h, w):
+    """(dh, dw) of the reference's 1.5x canvas for an h x w image."""
+    return int(h * 1.5 + 0.5), int(w * 1.5 + 0.5)
+
+
+def plate_window(dst_pts, dh, dw):
+    """(x0, y0, oh, ow) of the destination rectangle's pixels inside a dh x dw canvas, or None when empty: x0 = max(0, floor(min_x)),
+    x1 = min(dw-1, ceil(max_x)) inclusive, the same for y, over the float32 corner values the matrix is solved with."""
+    d = np.float32(dst_pts).reshape(4, 2).tolist()           # (float32 values as Python floats: exact)
+    xs, ys = [p[0] for p in d], [p[1] for p in d]
+    x0, x1 = max(0, math.floor(min(xs))), min(dw - 1, math.ceil(max(xs)))
+    y0, y1 = max(0, math.floor(min(ys))), min(dh - 1, math.ceil(max(ys)))
+    if x1 < x0 or y1 < y0:
+        return None
+    return x0, y0, y1 - y0 + 1, x1 - x0 + 1
+
+
+def _invertible(m):
+    """The test dbx_warp_perspective_batch_u8 applies to every map before it launches (warp_inverse and the finiteness check in
+    csrc/post_ops.hip; keep the two in step): every entry finite and the cofactor determinant, in the same operation order, non-zero.
+    A map that passes here is never refused there, so one bad quad gives None instead of failing the whole call."""
+    m = np.asarray(m, dtype=np.float64).reshape(9).tolist()
+    if not all(math.isfinite(v) for v in m):
+        return False
+    det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6])
+    return det != 0.0
+
+
+def _rect_job(quad, h, w, region):
+    """(m9, dh, dw, x0, y0, oh, ow) of one quad on an h x w image, or None (degenerate corners, a non-finite coordinate, an empty
+    plate window)."""
+    try:
+        q = np.asarray(quad, dtype=np.float64).reshape(4, 2)
+    except (TypeError, ValueError):
+        raise RuntimeError('perspective_transform_batch: a quad must be 4 (x, y) points, got %r' % (quad,))
+    if not np.all(np.isfinite(np.float32(q))):
+        return None
+    q = q.tolist()
+    dst = dst_rectangle(q)
+    try:
+        M = get_perspective_matrix(q, dst)
+    except RuntimeError:                                       # dbx_perspective_matrix: degenerate corner configuration
+        return None
+    if not _invertible(M):
+        return None
+    dh, dw = canvas_size(h, w)
+    if region == 'canvas':
+        return M, dh, dw, 0, 0, dh, dw
+    win = plate_window(dst, dh, dw)
+    return None if win is None else (M, dh, dw) + win
+
+
+def perspective_transform_batch(images, quads, *, region):
+    """perspective_transform over many images and many quads per image in ONE kernel launch (dbx_warp_perspective_batch_u8).
+
+    images: a uint8 [B,H,W,C] tensor, or a list of uint8 [H,W,C] images of any sizes (numpy arrays or tensors, on the CPU or the
+    GPU); C is 1..4 and the same for all.  Each image is copied to the device at most once.  quads[b]: the list of 4-point quads
+    (left-up, right-up, right-down, left-down) of image b.  region: 'canvas' -- the whole 1.5x canvas perspective_transform returns
+    -- or 'plate' -- its window over the destination rectangle (plate_window).  Every matrix comes from get_perspective_matrix on the
+    host.
+
+    Returns out[b][j]: uint8 [oh, ow, C] of the kind of image b (CUDA tensors are views into one device arena; numpy arrays and CPU
+    tensors come from one download of it), or None when the corners are degenerate, a coordinate is not finite or the plate window
+    is empty.  The pixels are bit for bit those of perspective_transform."""
+    check_region('perspective_transform_batch', region)
+    host, kinds = host_images('perspective_transform_batch', images, None)
+    if len(quads) != len(host):
+        raise RuntimeError('perspective_transform_batch: %d lists of quads for %d images' % (len(quads), len(host)))
+    return _warp_batch(to_device(images, host), kinds, quads, region)
+
+
+def host_images(who, images, channels):
+    """Checks a uint8 [B,H,W,C] tensor or a list of uint8 [H,W,C] images (numpy or torch) without touching the device: the list
+    of per-image tensors (torch views of numpy arrays) and the kind -- 'cuda', 'cpu' or 'numpy' -- of each.  channels: the one
+    channel count allowed, or None for 1..4."""
+    want = '3' if channels == 3 else 'C'
+    if torch.is_tensor(images):
+        if images.dtype != torch.uint8 or images.dim() != 4:
+            raise RuntimeError('%s: a tensor of images must be uint8 [B,H,W,%s], got %s %s' % (who, want, images.dtype, list(images.shape)))
+        ims = list(images.unbind(0))
+        kinds = ['cuda' if images.is_cuda else 'cpu'] * len(ims)
+    elif isinstance(images, (list, tuple)):
+        ims, kinds = [], []
+        for b, im in enumerate(images):
+            if isinstance(im, np.ndarray):
+                kinds.append('numpy')
+                im = torch.from_numpy(np.ascontiguousarray(im))
+            elif torch.is_tensor(im):
+                kinds.append('cuda' if im.is_cuda else 'cpu')
+            else:
+                raise RuntimeError('%s: images[%d] must be a numpy array or a tensor, got %s' % (who, b, type(im).__name__))
+            if im.dtype != torch.uint8 or im.dim() != 3:
+                raise RuntimeError('%s: images[%d] must be uint8 [H,W,%s], got %s %s' % (who, b, want, im.dtype, list(im.shape)))
+            ims.append(im)
+    else:
+        raise RuntimeError('%s: images must be a uint8 tensor or a list of images, got %s' % (who, type(images).__name__))
+    chans = sorted({int(im.size(2)) for im in ims})
+    if len(chans) > 1 or not set(chans) <= ({channels} if channels else {1, 2, 3, 4}):
+        raise RuntimeError('%s: every image needs %s channels, got %s' % (who, channels or 'the same count of 1..4', chans))
+    if len(ims) == 0:
+        raise RuntimeError('%s: no images' % who)
+    return ims, kinds
+
+
+def to_device(images, host):
+    """Device copies of host_images' list, each image uploaded at most once (a batch tensor in one copy)."""
+    if torch.is_tensor(images):
+        return list((images if images.is_cuda else images.cuda()).contiguous().unbind(0))
+    return [(im if im.is_cuda else im.cuda()).contiguous() for im in host]
+
+
+def _warp_batch(dev, kinds, quads, region):
+    """perspective_transform_batch on images already on the device: dev[b] a contiguous uint8 [H,W,C] CUDA tensor, kinds[b] the kind
+    ('cuda', 'cpu' or 'numpy') image b's results are returned as."""
+    c = int(dev[0].size(2))
+    out = [[None] * len(qs) for qs in quads]
+    spec, total = [], 0
+    for b, qs in enumerate(quads):
+        h, w = int(dev[b].size(0)), int(dev[b].size(1))
+        for j, q in enumerate(qs):
+            job = _rect_job(q, h, w, region)
+            if job is None:
+                continue
+            spec.append((b, j, total) + job)
+            total += (job[5] * job[6] * c + _ALIGN - 1) // _ALIGN * _ALIGN
+    if not spec:
+        return out
+    device = dev[0].device
+    arena = torch.empty(total, dtype=torch.uint8, device=device)
+    jobs = (_lib.WarpJob * len(spec))()
+    for r, (b, j, off, M, dh, dw, x0, y0, oh, ow) in zip(jobs, spec):
+        r.src = dev[b].data_ptr()
+        r.sh, r.sw = int(dev[b].size(0)), int(dev[b].size(1))
+        r.m9[:] = [float(v) for v in np.asarray(M, dtype=np.float64).reshape(9)]
+        r.dh, r.dw, r.x0, r.y0, r.oh, r.ow, r.dst_off = dh, dw, x0, y0, oh, ow, off
+    L = _lib.lib()
+    ws = torch.empty(L.dbx_warp_batch_workspace_bytes(len(spec)), dtype=torch.uint8, device=device)
+    check(L.dbx_warp_perspective_batch_u8(jobs, len(spec), c, C.c_void_p(arena.data_ptr()), C.c_void_p(ws.data_ptr()),
+                                          stream_ptr()))
+    host = arena.cpu() if any(kinds[b] != 'cuda' for b, *_ in spec) else None
+    for (b, j, off, M, dh, dw, x0, y0, oh, ow) in spec:
+        src = arena if kinds[b] == 'cuda' else host
+        v = src[off:off + oh * ow * c].view(oh, ow, c)
+        out[b][j] = v.numpy() if kinds[b] == 'numpy' else v
+    return out

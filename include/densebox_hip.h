@@ -47,8 +47,9 @@ const char* dbx_last_error(void);
  *      takes the fused heads forward (1 = ws / fragment-order weights as before, 2 = 8-phase / plain weights + plain second-weight image)
  *   7  (round 6) additions only: dbx_grad_guard, dbx_sgd_step_guarded, dbx_sgd_pack_step_guarded (f16 overflow guard), dbx_conv_wgrad_pool_dz; the heads-gen
  *      entry points accept DBX_F32 (reference instantiations for the parity suite)
- *   8  additions only: dbx_detect_batch, dbx_detect_batch_scratch_bytes (one decode + NMS launch over a batch of images) */
-#define DBX_ABI_VERSION 8
+ *   8  additions only: dbx_detect_batch, dbx_detect_batch_scratch_bytes (one decode + NMS launch over a batch of images)
+ *   9  additions only: dbx_warp_job, dbx_warp_perspective_batch_u8, dbx_warp_batch_workspace_bytes (every plate of a batch in one launch) */
+#define DBX_ABI_VERSION 9
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
 int dbx_device_arch(int device);
@@ -449,6 +450,25 @@ int dbx_nms(const double* dets, int32_t n, int32_t det_cols, double nms_thresh, 
 int dbx_perspective_matrix(const float* src_xy, const float* dst_xy, double* m9);
 int dbx_warp_perspective_u8(const uint8_t* src, int32_t sh, int32_t sw, int32_t c, const double* m9, uint8_t* dst,
                             int32_t dh, int32_t dw, void* stream);
+/* Batched warp: one launch over njobs jobs.  A job is one (source image, map, output window): it writes canvas rows y0..y0+oh-1,
+ * columns x0..x0+ow-1 of what dbx_warp_perspective_u8(src, sh, sw, c, m9, ., dh, dw) would write -- the same bits -- as a
+ * contiguous [oh][ow][c] block at byte offset dst_off of `dst` (64-bit offsets: arenas above 2 GiB are fine; any dst_off works, and
+ * a 16-byte aligned dst + dst_off is stored in 16-byte words for every c, a 4-byte aligned one in dwords, others byte by byte).  Jobs may read different images of different sizes; all share the channel count c (1..4).
+ * `jobs` is a HOST array: the library inverts every m9 and copies the device records into `workspace` (device,
+ * dbx_warp_batch_workspace_bytes(njobs) bytes) on `stream`, so the caller may reuse `jobs` when the call returns and must keep
+ * `workspace` until the launch has run.  Refused with DBX_ERR_ARG before anything is queued: njobs < 0, c outside 1..4, a null
+ * pointer, a non-positive size, a window outside its canvas, a negative dst_off, a non-finite or singular m9, more pixels than one
+ * grid holds (2^24 - 1 workgroups of 2048 pixels).  njobs == 0: no-op. */
+typedef struct dbx_warp_job {
+    const uint8_t* src;      /* device image [sh][sw][c] */
+    int32_t sh, sw;
+    double m9[9];            /* forward map src -> canvas, as for dbx_warp_perspective_u8 */
+    int32_t dh, dw;          /* canvas size (cv2 dsize) */
+    int32_t x0, y0, oh, ow;  /* window written: canvas rows y0..y0+oh-1, cols x0..x0+ow-1 */
+    int64_t dst_off;         /* byte offset of this job's [oh][ow][c] output in dst */
+} dbx_warp_job;
+int64_t dbx_warp_batch_workspace_bytes(int32_t njobs);
+int dbx_warp_perspective_batch_u8(const dbx_warp_job* jobs, int32_t njobs, int32_t c, uint8_t* dst, void* workspace, void* stream);
 
 /* ---- data-parallel gradient exchange (new capability; the reference is single-GPU) ----
  * One process per GPU.  Rank 0 makes a 128-byte id (dbx_dp_unique_id) and hands it to the other ranks by any host channel;
