@@ -54,6 +54,12 @@ class WarpJob(C.Structure):
                 ('dst_off', C.c_int64)]
 
 
+class ResizeJob(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('sh', C.c_int32), ('sw', C.c_int32), ('cx0', C.c_int32), ('cy0', C.c_int32),
+                ('cw', C.c_int32), ('ch', C.c_int32), ('pad_l', C.c_int32), ('pad_t', C.c_int32), ('pad_r', C.c_int32),
+                ('pad_b', C.c_int32), ('pad_value', C.c_int32), ('dh', C.c_int32), ('dw', C.c_int32), ('dst_off', C.c_int64)]
+
+
 _VP, _I32, _I64, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 _PV, _PC = C.POINTER(View), C.POINTER(ConvDesc)
 
@@ -101,6 +107,8 @@ SIGNATURES = {
     'dbx_warp_perspective_u8': (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP]),
     'dbx_warp_batch_workspace_bytes': (_I64, [_I32]),
     'dbx_warp_perspective_batch_u8': (C.c_int, [C.POINTER(WarpJob), _I32, _I32, _VP, _VP, _VP]),
+    'dbx_resize_batch_workspace_bytes': (_I64, [_I32]),
+    'dbx_resize_cubic_batch_u8': (C.c_int, [C.POINTER(ResizeJob), _I32, _I32, _VP, _VP, _VP]),
     'dbx_conv_wgrad_scratch_bytes': (_I64, [_I32, _PV, _PV, _I32, _I32]),
     'dbx_conv_wgrad': (C.c_int, [_I32, _PV, _PV, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _I32, _VP]),
     'dbx_conv_wgrad_slice': (C.c_int, [_I32, _PV, _PV, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP]),
@@ -145,7 +153,7 @@ SIGNATURES = {
     'dbx_nms': (C.c_int, [_VP, _I32, _I32, _D, _VP, _VP, _VP]),
 }
 
-ABI_VERSION = 9          # include/densebox_hip.h DBX_ABI_VERSION this binding was written against
+ABI_VERSION = 10         # include/densebox_hip.h DBX_ABI_VERSION this binding was written against
 _lib = None
 MISSING = []
 

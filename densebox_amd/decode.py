@@ -283,3 +283,40 @@ def detect_plates(net, images, K=10, nms_thresh=0.4, max_batch=32, *, region):
     quads = [[[[d[k, 5], d[k, 6]], [d[k, 7], d[k, 8]], [d[k, 9], d[k, 10]], [d[k, 11], d[k, 12]]] for k in keep] for d, keep in res]
     plates = rectify._warp_batch(dev, kinds, quads, region)
     return [(d, keep, p) for (d, keep), p in zip(res, plates)]
+
+
+def detect_batch_resized(net, images, size=720, K=10, nms_thresh=0.4, max_batch=32):
+    """detect_batch on frames of ANY sizes through the reference's own answer to mixed sizes: every frame is padded to a square with
+    grey 128 and resized to size x size with INTER_CUBIC (pad_img + cv2.resize, batch_pad_resize, DenseBox.py:1282-1340) in ONE
+    dbx_resize_cubic_batch_u8 launch, and the resulting uint8 [B, size, size, 3] tensor takes detect_batch's tensor path: a
+    mixed-size list runs in ceil(B / max_batch) forwards and replays ONE cached hipGraph shape.  The resize launch is NOT captured
+    (its job list depends on the call).
+
+    images: uint8 frames only -- a [B,H,W,3] tensor or a list of [H,W,3] images (numpy arrays or tensors); each is uploaded once.
+    size: a positive multiple of 4.
+
+    Returns, per image in input order, (dets, keep).  keep is detect_batch's for the resized frame, unchanged.  dets is its float64
+    row array with every coordinate column (0..3, and 5..12 for the landmark nets; column 4, the score, stays) mapped back to the
+    source frame in float64: x_src = x * (side / size) - pad_x, y_src = y * (side / size) - pad_y with
+    (side, pad_x, pad_y) = resize.pad_geometry(H, W).  So plates are rectified from the full-resolution frames by
+
+        res = net.detect_batch_resized(frames)
+        quads = [[[d[k, 5:7], d[k, 7:9], d[k, 9:11], d[k, 11:13]] for k in keep] for d, keep in res]
+        plates = rectify.perspective_transform_batch(frames, quads, region='plate')"""
+    from . import rectify, resize
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or size < 4 or size % 4:
+        raise RuntimeError('detect_batch_resized: size=%r must be a positive multiple of 4 (the maps are size / 4)' % (size,))
+    host, _ = rectify.host_images('detect_batch_resized', images, 3)
+    x = resize._pad_resize_device(rectify.to_device(images, host), int(size))
+    res = detect_batch(net, x, K, nms_thresh, max_batch)
+    out = []
+    for im, (d, keep) in zip(host, res):
+        side, pad_x, pad_y = resize.pad_geometry(im.size(0), im.size(1))
+        s = side / int(size)
+        d = d.copy()
+        xs = [0, 2] + list(range(5, d.shape[1], 2))
+        ys = [1, 3] + list(range(6, d.shape[1], 2))
+        d[:, xs] = d[:, xs] * s - pad_x
+        d[:, ys] = d[:, ys] * s - pad_y
+        out.append((d, keep))
+    return out

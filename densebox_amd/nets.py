@@ -135,6 +135,12 @@ class _DenseBoxBase(nn.Module):
         from .decode import detect_plates
         return detect_plates(self, images, K, nms_thresh, max_batch, region=region)
 
+    def detect_batch_resized(self, images, size=720, K=10, nms_thresh=0.4, max_batch=32):
+        """detect_batch() on uint8 frames of any sizes, each padded to a square and resized to size x size in one launch; a list of
+        (dets, keep) in input order, coordinates mapped back to the source frames (densebox_amd.decode.detect_batch_resized)."""
+        from .decode import detect_batch_resized
+        return detect_batch_resized(self, images, size, K, nms_thresh, max_batch)
+
 
 class DenseBox(_DenseBoxBase):
     KIND = 'DenseBox'

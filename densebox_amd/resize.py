@@ -1,0 +1,120 @@
+"""Pad + bicubic resize on the GPU: ``pad_img`` followed by ``cv2.resize(img, (size, size), interpolation=cv2.INTER_CUBIC)``
+(``batch_pad_resize``, DenseBox.py:1282-1340) and the patch cutters' ``cv2.resize`` of a cropped window
+(process_plate.py:244-252), over many images in ONE kernel launch (dbx_resize_cubic_batch_u8).  OpenCV is not part of the
+reference tree: the kernel restates the generic C path of its 8-bit INTER_CUBIC (see csrc/resize_ops.hip); parity with an
+OpenCV build is unpinned, and OpenCV's own SIMD builds may differ from that path in the last bit."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, stream_ptr
+from .rectify import host_images, to_device
+
+PAD_VALUE = 128
+
+
+def pad_geometry(h, w):
+    """(side, pad_x, pad_y) of pad_img on an h x w image: the side of the square, and the columns / rows added on the left / top
+    (the right / bottom gets the extra pixel of an odd difference)."""
+    h, w = int(h), int(w)
+    lu = abs(h - w) // 2
+    return max(h, w), (lu if h > w else 0), (lu if h <= w else 0)
+
+
+def pad_img(img):
+    """DenseBox.py:1282: pads the short side of a numpy [H,W] or [H,W,3] image to a square with grey 128."""
+    if not isinstance(img, np.ndarray):
+        raise RuntimeError('pad_img: the image must be a numpy array, got %s' % type(img).__name__)
+    if not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
+        raise RuntimeError('pad_img: the image must be [H,W] or [H,W,3], got %s' % list(img.shape))
+    h, w = img.shape[:2]
+    side, px, py = pad_geometry(h, w)
+    padding = ((py, side - h - py), (px, side - w - px)) + ((0, 0),) * (img.ndim - 2)
+    return np.pad(img, padding, 'constant', constant_values=PAD_VALUE)
+
+
+def _resize_jobs(dev, spec, c):
+    """ONE launch over spec = [(b, cx0, cy0, cw, ch, pad_l, pad_t, pad_r, pad_b, dh, dw)], all with the same dh x dw: the uint8
+    [len(spec), dh, dw, c] CUDA tensor of the jobs' results in order.  dev[b]: contiguous uint8 [H,W,c] CUDA tensors."""
+    dh, dw = spec[0][9], spec[0][10]
+    block = dh * dw * c            # the jobs' blocks back to back ARE the result: the kernel stores aligned words at any offset
+    device = dev[0].device
+    out = torch.empty((len(spec), dh, dw, c), dtype=torch.uint8, device=device)
+    jobs = (_lib.ResizeJob * len(spec))()
+    for i, (r, (b, cx0, cy0, cw, ch, pl, pt, pr, pb, jh, jw)) in enumerate(zip(jobs, spec)):
+        r.src = dev[b].data_ptr()
+        r.sh, r.sw = int(dev[b].size(0)), int(dev[b].size(1))
+        r.cx0, r.cy0, r.cw, r.ch = cx0, cy0, cw, ch
+        r.pad_l, r.pad_t, r.pad_r, r.pad_b, r.pad_value = pl, pt, pr, pb, PAD_VALUE
+        r.dh, r.dw, r.dst_off = jh, jw, i * block
+    L = _lib.lib()
+    ws = torch.empty(L.dbx_resize_batch_workspace_bytes(len(spec)), dtype=torch.uint8, device=device)
+    check(L.dbx_resize_cubic_batch_u8(jobs, len(spec), c, C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), stream_ptr()))
+    return out
+
+
+def _check_size(who, size):
+    try:
+        w, h = (size, size) if isinstance(size, (int, np.integer)) else (int(size[0]), int(size[1]))
+    except (TypeError, ValueError, IndexError):
+        raise RuntimeError('%s: size must be an integer or (width, height), got %r' % (who, size))
+    if w < 1 or h < 1:
+        raise RuntimeError('%s: size=%r must be positive' % (who, size))
+    return int(w), int(h)
+
+
+def _pad_resize_device(dev, size):
+    """pad_resize_batch on images already on the device."""
+    spec = []
+    for b, im in enumerate(dev):
+        h, w = int(im.size(0)), int(im.size(1))
+        side, px, py = pad_geometry(h, w)
+        spec.append((b, 0, 0, w, h, px, py, side - w - px, side - h - py, size, size))
+    return _resize_jobs(dev, spec, int(dev[0].size(2)))
+
+
+def pad_resize_batch(images, size=720):
+    """batch_pad_resize's pixel work (DenseBox.py:1317-1340) in ONE kernel launch: per image, cv2.resize(pad_img(im), (size, size),
+    interpolation=cv2.INTER_CUBIC).  The padded square is never materialised.
+
+    images: a uint8 [B,H,W,C] tensor, or a list of uint8 [H,W,C] images of any sizes (numpy arrays or tensors, on the CPU or the
+    GPU); C is 1..4 and the same for all.  Each image is copied to the device at most once.  Returns a uint8 [B, size, size, C]
+    CUDA tensor."""
+    if not isinstance(size, (int, np.integer)) or size < 1:
+        raise RuntimeError('pad_resize_batch: size must be a positive integer (the side of the square), got %r' % (size,))
+    host, _ = host_images('pad_resize_batch', images, None)
+    return _pad_resize_device(to_device(images, host), int(size))
+
+
+def crop_resize_batch(images, windows, size=(240, 240)):
+    """The pixel half of the reference's patch cutters in ONE kernel launch: per image b and window (x0, y0, x1, y1) of windows[b],
+    cv2.resize(img[y0:y1, x0:x1], size, interpolation=cv2.INTER_CUBIC).  Windows are integers with Python-slice semantics
+    (negative values count from the end and both ends are clamped to the image, as a numpy slice does); an empty slice is refused.
+
+    images: as for pad_resize_batch.  size: (width, height) as in cv2.  Returns a uint8 [P, height, width, C] CUDA tensor in
+    image-then-window order."""
+    dw, dh = _check_size('crop_resize_batch', size)
+    host, _ = host_images('crop_resize_batch', images, None)
+    if not isinstance(windows, (list, tuple)) or len(windows) != len(host):
+        raise RuntimeError('crop_resize_batch: %s lists of windows for %d images'
+                           % (len(windows) if isinstance(windows, (list, tuple)) else 'no', len(host)))
+    spec = []
+    for b, (im, wins) in enumerate(zip(host, windows)):
+        h, w = int(im.size(0)), int(im.size(1))
+        for win in wins:
+            try:
+                x0, y0, x1, y1 = (int(v) for v in win)
+                if any(int(v) != v for v in win):
+                    raise ValueError
+            except (TypeError, ValueError):
+                raise RuntimeError('crop_resize_batch: a window must be 4 integers (x0, y0, x1, y1), got %r for image %d' % (win, b))
+            xa, xb, _ = slice(x0, x1).indices(w)
+            ya, yb, _ = slice(y0, y1).indices(h)
+            if xb <= xa or yb <= ya:
+                raise RuntimeError('crop_resize_batch: window %r of image %d (%d x %d) is an empty slice' % (tuple(win), b, h, w))
+            spec.append((b, xa, ya, xb - xa, yb - ya, 0, 0, 0, 0, dh, dw))
+    if not spec:
+        raise RuntimeError('crop_resize_batch: no windows')
+    return _resize_jobs(to_device(images, host), spec, int(host[0].size(2)))

@@ -48,8 +48,9 @@ const char* dbx_last_error(void);
  *   7  (round 6) additions only: dbx_grad_guard, dbx_sgd_step_guarded, dbx_sgd_pack_step_guarded (f16 overflow guard), dbx_conv_wgrad_pool_dz; the heads-gen
  *      entry points accept DBX_F32 (reference instantiations for the parity suite)
  *   8  additions only: dbx_detect_batch, dbx_detect_batch_scratch_bytes (one decode + NMS launch over a batch of images)
- *   9  additions only: dbx_warp_job, dbx_warp_perspective_batch_u8, dbx_warp_batch_workspace_bytes (every plate of a batch in one launch) */
-#define DBX_ABI_VERSION 9
+ *   9  additions only: dbx_warp_job, dbx_warp_perspective_batch_u8, dbx_warp_batch_workspace_bytes (every plate of a batch in one launch)
+ *  10  additions only: dbx_resize_job, dbx_resize_cubic_batch_u8, dbx_resize_batch_workspace_bytes (batched pad + bicubic resize) */
+#define DBX_ABI_VERSION 10
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
 int dbx_device_arch(int device);
@@ -469,6 +470,38 @@ typedef struct dbx_warp_job {
 } dbx_warp_job;
 int64_t dbx_warp_batch_workspace_bytes(int32_t njobs);
 int dbx_warp_perspective_batch_u8(const dbx_warp_job* jobs, int32_t njobs, int32_t c, uint8_t* dst, void* workspace, void* stream);
+
+/* ---- batched pad + bicubic resize (pad_img + cv2.resize(..., INTER_CUBIC), DenseBox.py:1282-1340; the patch cutters' resize of a
+ * cropped window) ----
+ * One launch over njobs jobs.  A job reads a VIRTUAL source: the crop [cy0, cy0 + ch) x [cx0, cx0 + cw) of an interleaved uint8 image
+ * [sh][sw][c] with pad_l / pad_t / pad_r / pad_b columns / rows of the constant pad_value around it -- what np.pad of the crop gives,
+ * never materialised -- of vh x vw = (ch + pad_t + pad_b) x (cw + pad_l + pad_r) pixels, and writes its dh x dw resize as a contiguous
+ * [dh][dw][c] block at byte offset dst_off of `dst` (64-bit; any alignment: whole 16-byte words of a row are stored as such, the
+ * partial first / last word of a row as dwords, then bytes, and no byte outside the block is written).
+ * Arithmetic: the generic C path of OpenCV's 8-bit INTER_CUBIC, restated.  Column dx: fx = (float)((dx + 0.5) * ((double)vw / dw) - 0.5),
+ * sx = floor(fx), fx -= sx; float coefficients with A = -0.75 (c0 = ((A*(fx+1) - 5A)*(fx+1) + 8A)*(fx+1) - 4A, c1 = ((A+2)*fx - (A+3))*fx*fx + 1,
+ * c2 the same in 1 - fx, c3 = 1 - c0 - c1 - c2), each rounded to int16 as saturate(rint(c * 2048)), no sum correction; taps sx-1 .. sx+2
+ * clamped to [0, vw - 1] (replicate border of the virtual source).  Rows alike.  acc = sum of beta * alpha * pixel in int32
+ * (|acc| <= 255 * (1.375 * 2048)^2 < 2^31); out = saturate_u8((acc + 2^21) >> 22).  Parity with an OpenCV build is unpinned.
+ * Jobs may read different images of different sizes and write different sizes; all share the channel count c (1..4).  `jobs` is a
+ * HOST array: the library copies its device records into `workspace` (device, dbx_resize_batch_workspace_bytes(njobs) bytes) on
+ * `stream`, so the caller may reuse `jobs` when the call returns and must keep `workspace` until the launch has run.  Refused with
+ * DBX_ERR_ARG before anything is queued: njobs < 0, c outside 1..4, a null pointer, a non-positive size, an image above 2^31 - 1
+ * bytes, a crop outside its image, negative padding, a padded side above 2^30, pad_value outside 0..255, a negative dst_off, more
+ * tiles than one grid holds (2^24 - 1 workgroups of 16 x 64 pixels).  njobs == 0: no-op.
+ * Layout (72 bytes): src 0, sh 8, sw 12, cx0 16, cy0 20, cw 24, ch 28, pad_l 32, pad_t 36, pad_r 40, pad_b 44, pad_value 48, dh 52,
+ * dw 56, (4 bytes of alignment padding,) dst_off 64. */
+typedef struct dbx_resize_job {
+    const uint8_t* src;                      /* device image [sh][sw][c] */
+    int32_t sh, sw;
+    int32_t cx0, cy0, cw, ch;                /* crop window inside the image */
+    int32_t pad_l, pad_t, pad_r, pad_b;      /* constant padding around the crop */
+    int32_t pad_value;                       /* 0..255 */
+    int32_t dh, dw;                          /* destination size */
+    int64_t dst_off;                         /* byte offset of this job's [dh][dw][c] output in dst */
+} dbx_resize_job;
+int64_t dbx_resize_batch_workspace_bytes(int32_t njobs);
+int dbx_resize_cubic_batch_u8(const dbx_resize_job* jobs, int32_t njobs, int32_t c, uint8_t* dst, void* workspace, void* stream);
 
 /* ---- data-parallel gradient exchange (new capability; the reference is single-GPU) ----
  * One process per GPU.  Rank 0 makes a 128-byte id (dbx_dp_unique_id) and hands it to the other ranks by any host channel;
