@@ -60,6 +60,10 @@ class ResizeJob(C.Structure):
                 ('pad_b', C.c_int32), ('pad_value', C.c_int32), ('dh', C.c_int32), ('dw', C.c_int32), ('dst_off', C.c_int64)]
 
 
+class MergeXform(C.Structure):
+    _fields_ = [('scale', C.c_double), ('off_x', C.c_double), ('off_y', C.c_double)]
+
+
 _VP, _I32, _I64, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 _PV, _PC = C.POINTER(View), C.POINTER(ConvDesc)
 
@@ -151,9 +155,11 @@ SIGNATURES = {
     'dbx_detect_batch_scratch_bytes': (_I64, [_I32, _I32, _I32, _I32]),
     'dbx_detect_batch': (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _D, _VP, _I32, _VP, _VP, _VP, _VP]),
     'dbx_nms': (C.c_int, [_VP, _I32, _I32, _D, _VP, _VP, _VP]),
+    'dbx_merge_nms_batch_workspace_bytes': (_I64, [_I32, _I32, _I32]),
+    'dbx_merge_nms_batch': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(MergeXform), _I32, _I32, _I32, _I32, _D, _VP, _VP, _VP, _VP]),
 }
 
-ABI_VERSION = 10         # include/densebox_hip.h DBX_ABI_VERSION this binding was written against
+ABI_VERSION = 11         # include/densebox_hip.h DBX_ABI_VERSION this binding was written against
 _lib = None
 MISSING = []
 

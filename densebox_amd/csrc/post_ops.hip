@@ -5,6 +5,7 @@
 #include "common.hpp"
 
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 // ---------------------------------------------------------------------------------------------- SGD (DenseBox.py:2001-2004)
@@ -123,16 +124,19 @@ __device__ __forceinline__ void block_argmax_cached(float bv, int bi, float* red
 __device__ void nms_block(const double* dets, int n, int dc, double thresh, int* keep, int* order, unsigned char* supp,
                           unsigned long long* mask = nullptr) {
     const int tid = threadIdx.x, nt = blockDim.x;
-    // (NaN scores compare false both ways: the ranks below are then not a permutation -- a diverged network must give a strange
-    // order, never an out-of-range row index: every slot starts as a valid row)
+    // NaN scores rank where NumPy's sort puts them: argsort leaves NaN last, so [::-1] has them FIRST, the higher row index first among
+    // them.  (NaN compares false both ways: ranked by `>` and `==` alone, every NaN row and the best row shared rank 0 -- not a
+    // permutation, and which of them landed in the slot was a race between their threads.)  Every slot still starts as a valid row.
     for (int i = tid; i < n; i += nt) order[i] = i;
     __syncthreads();
     for (int i = tid; i < n; i += nt) {
         const double si = dets[(size_t)i * dc + 4];
+        const bool nan_i = si != si;
         int rank = 0;
         for (int j = 0; j < n; ++j) {
             const double sj = dets[(size_t)j * dc + 4];
-            rank += (sj > si) || (sj == si && j > i);
+            const bool nan_j = sj != sj;
+            rank += nan_i ? (nan_j && j > i) : (nan_j || (sj > si) || (sj == si && j > i));
         }
         order[rank] = i;
         supp[i] = 0;
@@ -578,6 +582,89 @@ extern "C" int dbx_nms(const double* dets, int32_t n, int32_t det_cols, double n
     int* order = (int*)scratch;
     unsigned char* supp = (unsigned char*)scratch + (size_t)n * 4;
     hipLaunchKernelGGL(nms_kernel, dim3(1), dim3(DET_THREADS), 0, (hipStream_t)stream, dets, n, det_cols, nms_thresh, keep, order, supp);
+    DBX_LAUNCH_CHECK();
+    return DBX_OK;
+}
+
+// ---- pyramid merge: the rows of every level of every frame of a chunk mapped back to the source frame + ONE greedy NMS per frame over
+// their union, in one launch (dbx_merge_nms_batch).  Workgroup b owns frame b.  Stage 1 copies row r of level l to row l * K + r of
+// out_dets[b] with x * scale - off_x / y * scale - off_y in float64 (contraction is off in this file: the product is rounded before
+// the subtraction, NumPy's `d * scale - off` bit for bit; the score column is copied).  Stage 2, after a barrier, is nms_block on those
+// n = levels * K rows -- the code dbx_nms runs, at the same workgroup width, so order, ties, the +1 pixel IoU and the NaN handling
+// cannot drift apart.  The map stage uses no LDS; nms_block's static arrays are the kernel's whole LDS budget.
+// workspace: [levels device pointers][levels * batch transforms] rounded to 256 B, then one slice per frame:
+// order (4 n, to 256 B) | suppression flags (n, to 256 B) | the 16-word suppression rows (128 n, only when n <= NMS_LDS_MAX)
+#define MERGE_MAX_ROWS 4096
+static int64_t merge_head_bytes(int32_t levels, int32_t batch) {
+    return ((int64_t)levels * 8 + (int64_t)levels * batch * (int64_t)sizeof(dbx_merge_xform) + 255) / 256 * 256;
+}
+static int64_t merge_slice_bytes(int64_t n) {
+    return (n * 4 + 255) / 256 * 256 + (n + 255) / 256 * 256 + (n <= NMS_LDS_MAX ? (n * 128 + 255) / 256 * 256 : 0);
+}
+static_assert(sizeof(dbx_merge_xform) == 24, "dbx_merge_xform layout");
+
+__global__ __launch_bounds__(DET_THREADS) void merge_nms_kernel(const double* const* __restrict__ level_dets,
+                                                                const dbx_merge_xform* __restrict__ xform, int levels, int batch, int K,
+                                                                int dc, double thresh, double* __restrict__ out_dets, int* out_keep,
+                                                                unsigned char* slices, long long slice_bytes) {
+    const size_t b = blockIdx.x;
+    const int n = levels * K;                                   // <= MERGE_MAX_ROWS
+    const long long ne = (long long)n * dc;
+    double* const o = out_dets + b * (size_t)ne;
+    for (long long e = threadIdx.x; e < ne; e += blockDim.x) {
+        const int row = (int)(e / dc), col = (int)(e - (long long)row * dc);
+        const int l = row / K, r = row - l * K;
+        double v = level_dets[l][(b * (size_t)K + (size_t)r) * (size_t)dc + (size_t)col];
+        if (col != 4) {
+            const dbx_merge_xform t = xform[(size_t)l * batch + b];
+            const bool is_x = col < 4 ? !(col & 1) : (col & 1);   // x: 0, 2, 5, 7, 9, 11; y: 1, 3, 6, 8, 10, 12
+            v = v * t.scale - (is_x ? t.off_x : t.off_y);
+        }
+        o[e] = v;
+    }
+    __threadfence_block();
+    __syncthreads();
+    unsigned char* s = slices + b * (size_t)slice_bytes;
+    int* order = (int*)s;
+    unsigned char* supp = s + ((size_t)n * 4 + 255) / 256 * 256;
+    unsigned long long* mask = n <= NMS_LDS_MAX ? (unsigned long long*)(supp + ((size_t)n + 255) / 256 * 256) : nullptr;
+    nms_block(o, n, dc, thresh, out_keep + b * ((size_t)n + 1), order, supp, mask);
+}
+
+extern "C" int64_t dbx_merge_nms_batch_workspace_bytes(int32_t levels, int32_t batch, int32_t K) {
+    if (levels < 1 || batch < 1 || K < 1 || (int64_t)levels * K > MERGE_MAX_ROWS) return -1;
+    return merge_head_bytes(levels, batch) + (int64_t)batch * merge_slice_bytes((int64_t)levels * K);
+}
+
+extern "C" int dbx_merge_nms_batch(const double* const* level_dets, const dbx_merge_xform* xform, int32_t levels, int32_t batch, int32_t K,
+                                   int32_t det_cols, double nms_thresh, double* out_dets, int32_t* out_keep, void* workspace,
+                                   void* stream) {
+    DBX_REQUIRE(levels >= 1, "merge_nms_batch: levels=%d must be positive", levels);
+    DBX_REQUIRE(batch >= 1, "merge_nms_batch: batch=%d must be positive", batch);
+    DBX_REQUIRE(K >= 1, "merge_nms_batch: K=%d must be positive", K);
+    DBX_REQUIRE(det_cols == 5 || det_cols == 13, "merge_nms_batch: det_cols=%d must be 5 or 13", det_cols);
+    DBX_REQUIRE((int64_t)levels * K <= MERGE_MAX_ROWS, "merge_nms_batch: levels * K = %lld rows per frame exceed %d (the rank pass is quadratic)",
+                (long long)levels * K, MERGE_MAX_ROWS);
+    DBX_REQUIRE(level_dets && xform && out_dets && out_keep && workspace, "merge_nms_batch: null argument");
+    for (int l = 0; l < levels; ++l) DBX_REQUIRE(level_dets[l], "merge_nms_batch: level %d has a null row pointer", l);
+    for (int64_t i = 0; i < (int64_t)levels * batch; ++i) {
+        const dbx_merge_xform& t = xform[i];
+        DBX_REQUIRE(std::isfinite(t.scale) && t.scale > 0.0, "merge_nms_batch: level %d frame %d has scale %g (finite and positive needed)",
+                    (int)(i / batch), (int)(i % batch), t.scale);
+        DBX_REQUIRE(std::isfinite(t.off_x) && std::isfinite(t.off_y), "merge_nms_batch: level %d frame %d has a non-finite offset",
+                    (int)(i / batch), (int)(i % batch));
+    }
+    // device records: the level pointers, then the transforms.  Pageable host source: the copy has read the vector when it returns,
+    // so it may go out of scope (and the caller's arrays be reused)
+    const int64_t head = merge_head_bytes(levels, batch);
+    std::vector<unsigned char> rec((size_t)head, 0);
+    memcpy(rec.data(), level_dets, (size_t)levels * 8);
+    memcpy(rec.data() + (size_t)levels * 8, xform, (size_t)levels * batch * sizeof(dbx_merge_xform));
+    unsigned char* ws = (unsigned char*)workspace;
+    DBX_HIP(hipMemcpyAsync(ws, rec.data(), (size_t)head, hipMemcpyHostToDevice, (hipStream_t)stream));
+    hipLaunchKernelGGL(merge_nms_kernel, dim3(batch), dim3(DET_THREADS), 0, (hipStream_t)stream, (const double* const*)ws,
+                       (const dbx_merge_xform*)(ws + (size_t)levels * 8), levels, batch, K, det_cols, nms_thresh, out_dets, out_keep,
+                       ws + head, (long long)merge_slice_bytes((int64_t)levels * K));
     DBX_LAUNCH_CHECK();
     return DBX_OK;
 }

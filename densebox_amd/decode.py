@@ -115,11 +115,14 @@ def _detect_batch_eager(net, images, K, nms_thresh):
     return dets, keep
 
 
-def _graph_replay(net, tag, image, K, nms_thresh, eager):
+def _graph_replay(net, tag, image, K, nms_thresh, eager, to_host=True):
     """Replays (capturing on the first call) one hipGraph of eager(net, image, K, nms_thresh) -> (dets, keep) device tensors
     and returns the two results in pinned host tensors, valid until the next call.  One cache per network, shared by
-    detect() and detect_batch(): keyed by (tag, input shape, input dtype, K, threshold, compute dtype), re-captured when the
-    weight signature changes, at most _MAX_GRAPHS entries (LRU)."""
+    detect(), detect_batch() and detect_pyramid(): keyed by (tag, input shape, input dtype, K, threshold, compute dtype),
+    re-captured when the weight signature changes, at most _MAX_GRAPHS entries (LRU).
+
+    to_host=False (detect_pyramid's 'level' entries): nothing is copied and nothing waits -- the replay is queued and the entry's
+    own device (dets, keep) are returned, valid in stream order until the entry's next replay."""
     import collections
     cache = net.__dict__.setdefault('_detect_graphs', collections.OrderedDict())
     # weight signature: versions + storage addresses of every parameter (a replay reads the packed copies made at capture).
@@ -141,16 +144,30 @@ def _graph_replay(net, tag, image, K, nms_thresh, eager):
         static_in = image.clone()
         for _ in range(2):                       # warm: workspace plan, packed weights, scratch buffers, kernel attributes
             wd, wk = eager(net, static_in, K, nms_thresh)
-        h_dets = torch.empty(wd.shape, dtype=wd.dtype).pin_memory()        # (pinned allocation is not capturable)
-        h_keep = torch.empty(wk.shape, dtype=wk.dtype).pin_memory()
+        h_dets = h_keep = None
+        if to_host:
+            h_dets = torch.empty(wd.shape, dtype=wd.dtype).pin_memory()        # (pinned allocation is not capturable)
+            h_keep = torch.empty(wk.shape, dtype=wk.dtype).pin_memory()
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            dets, keep = eager(net, static_in, K, nms_thresh)
-            # the two result copies are graph nodes too (pinned destinations): one replay + one stream sync per call
-            # instead of two blocking .cpu() calls with their launch round trips (~60 us of idle GPU per call)
-            h_dets.copy_(dets, non_blocking=True)
-            h_keep.copy_(keep, non_blocking=True)
+        # No cyclic garbage collection DURING the capture: a dead network (modules sit in reference cycles) takes its cached graphs
+        # with it, and destroying a graph while a stream captures is an error that ends the process.  Collect what is dead now, then
+        # keep the collector off until the capture has ended (torch.cuda.graph no longer collects on entry).
+        import gc
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g):
+                dets, keep = eager(net, static_in, K, nms_thresh)
+                # the two result copies are graph nodes too (pinned destinations): one replay + one stream sync per call
+                # instead of two blocking .cpu() calls with their launch round trips (~60 us of idle GPU per call)
+                if to_host:
+                    h_dets.copy_(dets, non_blocking=True)
+                    h_keep.copy_(keep, non_blocking=True)
+        finally:
+            if gc_was_on:
+                gc.enable()
         # The captured kernels hold RAW pointers into the engine's workspace plan and packed / folded weight buffers.  The
         # engine keeps one plan and re-creates its weight caches when the dtype or mode flips, so the entry pins every
         # tensor it captured: a later forward at another shape (or a train-mode step) cannot free what a replay reads.
@@ -162,6 +179,8 @@ def _graph_replay(net, tag, image, K, nms_thresh, eager):
     _, g, static_in, dets, keep, _refs, h_dets, h_keep = ent
     static_in.copy_(image)
     g.replay()
+    if not to_host:
+        return dets, keep
     torch.cuda.current_stream().synchronize()
     return h_dets, h_keep
 
@@ -320,3 +339,91 @@ def detect_batch_resized(net, images, size=720, K=10, nms_thresh=0.4, max_batch=
         d[:, ys] = d[:, ys] * s - pad_y
         out.append((d, keep))
     return out
+
+
+_PYRAMID_MAX_LEVELS = 4          # each level (and possibly its tail chunk) owns a cached graph shape, and _MAX_GRAPHS is 8
+_MERGE_MAX_ROWS = 4096           # dbx_merge_nms_batch's bound on levels * K
+
+
+def _check_pyramid_sizes(sizes):
+    ok = isinstance(sizes, (list, tuple)) and 1 <= len(sizes) <= _PYRAMID_MAX_LEVELS
+    ok = ok and all(isinstance(s, (int, np.integer)) and not isinstance(s, (bool, np.bool_)) and s >= 4 and s % 4 == 0 for s in sizes)
+    if not ok or len({int(s) for s in sizes}) != len(sizes):
+        raise RuntimeError('detect_pyramid: sizes=%r must be 1 to %d distinct positive multiples of 4 (the maps are size / 4; every '
+                           'level owns a cached graph shape)' % (sizes, _PYRAMID_MAX_LEVELS))
+    return [int(s) for s in sizes]
+
+
+def _merge_nms(level_dets, xform, nms_thresh, out_dets, out_keep):
+    """ONE dbx_merge_nms_batch launch: level_dets a list of L device [b, K, dc] float64 tensors, xform [L][b] (scale, off_x, off_y)
+    triples, out_dets [b, L * K, dc] / out_keep [b, L * K + 1] device tensors (views of larger ones are fine: both are dense)."""
+    levels, (b, K, dc) = len(level_dets), level_dets[0].shape
+    ptrs = (C.c_void_p * levels)(*[t.data_ptr() for t in level_dets])
+    xf = (_lib.MergeXform * (levels * b))()
+    for l in range(levels):
+        for i in range(b):
+            xf[l * b + i].scale, xf[l * b + i].off_x, xf[l * b + i].off_y = xform[l][i]
+    L = _lib.lib()
+    nbytes = L.dbx_merge_nms_batch_workspace_bytes(levels, b, K)
+    if nbytes < 0:
+        raise RuntimeError('detect_pyramid: %d levels x K=%d rows per frame exceed %d' % (levels, K, _MERGE_MAX_ROWS))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=out_dets.device)
+    check(L.dbx_merge_nms_batch(ptrs, xf, levels, b, K, dc, float(nms_thresh), ptr(out_dets), ptr(out_keep), ptr(ws), stream_ptr()))
+
+
+def detect_pyramid(net, images, sizes=(480, 720, 1080), K=10, nms_thresh=0.4, max_batch=32):
+    """Multi-scale detection, the test-time image pyramid of the DenseBox paper: every frame is padded to a square and resized to
+    EVERY size of `sizes` (what detect_batch_resized does for one size) in ONE dbx_resize_cubic_batch_u8 launch; per chunk of at most
+    `max_batch` frames each level runs one forward + one dbx_detect_batch (in eval mode a cached hipGraph per level shape whose rows
+    stay on the device), and ONE dbx_merge_nms_batch launch maps the rows of all levels back to the source frames and runs the
+    reference's greedy NMS over their union, a workgroup per frame.  One copy brings the results of the call to the host.  The resize
+    and the merge launches are not captured; train mode and DBX_GRAPH=0 run the same launches eagerly.
+
+    images: uint8 frames only -- a [B,H,W,3] tensor or a list of [H,W,3] images (numpy arrays or tensors, on the CPU or the GPU) of
+    any sizes; each is uploaded at most once.  sizes: 1 to 4 distinct positive multiples of 4.  The default is the reference's single
+    720 (batch_pad_resize) with 2/3 and 3/2 of it: a convention, NOT a tuned value -- no trained weights exist in this tree to tune
+    it with.  K: rows per level (len(sizes) * K <= 4096).
+
+    Returns, per frame in input order, (dets, keep): dets the float64 [len(sizes) * K, 5|13] rows in SOURCE-frame coordinates, level
+    by level in the order of `sizes` (row l * K + r is row r of detect_batch_resized(..., size=sizes[l]); x_src = x * (side / size) -
+    pad_x, y_src = y * (side / size) - pad_y with (side, pad_x, pad_y) = resize.pad_geometry(H, W)), and keep the row indices the NMS
+    over all of them keeps, in the reference's order (the level of a kept row is index // K).  So plates are rectified from the
+    full-resolution frames by
+
+        res = net.detect_pyramid(frames)
+        quads = [[[d[k, 5:7], d[k, 7:9], d[k, 9:11], d[k, 11:13]] for k in keep] for d, keep in res]
+        plates = rectify.perspective_transform_batch(frames, quads, region='plate')"""
+    import os
+    from . import rectify, resize
+    sizes = _check_pyramid_sizes(sizes)
+    if isinstance(max_batch, bool) or not isinstance(max_batch, (int, np.integer)) or max_batch < 1:
+        raise RuntimeError('detect_pyramid: max_batch=%r must be a positive integer' % (max_batch,))
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1 or len(sizes) * K > _MERGE_MAX_ROWS:
+        raise RuntimeError('detect_pyramid: K=%r must be a positive integer with len(sizes) * K <= %d' % (K, _MERGE_MAX_ROWS))
+    host, _ = rectify.host_images('detect_pyramid', images, 3)
+    K, max_batch, B, nl = int(K), int(max_batch), len(host), len(sizes)
+    dev = rectify.to_device(images, host)
+    levels = resize._pad_resize_levels(dev, sizes)
+    xform = [[resize.level_xform(im.size(0), im.size(1), s) for im in host] for s in sizes]
+    graph = not net.training and os.environ.get('DBX_GRAPH', '1') != '0'
+    dc = 5 if net.KIND == 'DenseBox' else 13
+    n = nl * K
+    # one device buffer for the whole call: [B][n][dc] float64 rows, then [B][n + 1] int32 keep lists -- a single copy to the host
+    nd = B * n * dc * 8
+    buf = torch.empty(nd + B * (n + 1) * 4, dtype=torch.uint8, device=dev[0].device)
+    out_dets, out_keep = buf[:nd].view(torch.float64).view(B, n, dc), buf[nd:].view(torch.int32).view(B, n + 1)
+    for c0 in range(0, B, max_batch):
+        c1 = min(B, c0 + max_batch)
+        rows = []
+        for lv in levels:
+            x = lv[c0:c1]
+            if graph:        # the entry's device rows: overwritten by its next replay, which is queued behind this chunk's merge
+                d, _ = _graph_replay(net, 'level', x, K, nms_thresh, _detect_batch_eager, to_host=False)
+            else:
+                d, _ = _detect_batch_eager(net, x, K, nms_thresh)
+            rows.append(d)
+        _merge_nms(rows, [xf[c0:c1] for xf in xform], nms_thresh, out_dets[c0:c1], out_keep[c0:c1])
+    h = buf.cpu()
+    d = h[:nd].view(torch.float64).view(B, n, dc).numpy()
+    k = h[nd:].view(torch.int32).view(B, n + 1).numpy()
+    return [(d[b].copy(), [int(v) for v in k[b, 1:1 + int(k[b, 0])]]) for b in range(B)]

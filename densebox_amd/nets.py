@@ -141,6 +141,13 @@ class _DenseBoxBase(nn.Module):
         from .decode import detect_batch_resized
         return detect_batch_resized(self, images, size, K, nms_thresh, max_batch)
 
+    def detect_pyramid(self, images, sizes=(480, 720, 1080), K=10, nms_thresh=0.4, max_batch=32):
+        """detect_batch_resized() at every size of `sizes` with one resize launch, the rows of all levels merged in source-frame
+        coordinates and ONE NMS per frame over their union on the device; a list of (dets[len(sizes) * K, 5|13], keep) in input
+        order (densebox_amd.decode.detect_pyramid)."""
+        from .decode import detect_pyramid
+        return detect_pyramid(self, images, sizes, K, nms_thresh, max_batch)
+
 
 class DenseBox(_DenseBoxBase):
     KIND = 'DenseBox'

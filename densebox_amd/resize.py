@@ -35,23 +35,28 @@ def pad_img(img):
     return np.pad(img, padding, 'constant', constant_values=PAD_VALUE)
 
 
+def _launch_jobs(dev, spec, offs, c, arena):
+    """ONE dbx_resize_cubic_batch_u8 launch over spec = [(b, cx0, cy0, cw, ch, pad_l, pad_t, pad_r, pad_b, dh, dw)], job i writing its
+    [dh, dw, c] block at byte offs[i] of the uint8 CUDA tensor `arena`.  dev[b]: contiguous uint8 [H,W,c] CUDA tensors."""
+    jobs = (_lib.ResizeJob * len(spec))()
+    for r, (b, cx0, cy0, cw, ch, pl, pt, pr, pb, jh, jw), off in zip(jobs, spec, offs):
+        r.src = dev[b].data_ptr()
+        r.sh, r.sw = int(dev[b].size(0)), int(dev[b].size(1))
+        r.cx0, r.cy0, r.cw, r.ch = cx0, cy0, cw, ch
+        r.pad_l, r.pad_t, r.pad_r, r.pad_b, r.pad_value = pl, pt, pr, pb, PAD_VALUE
+        r.dh, r.dw, r.dst_off = jh, jw, off
+    L = _lib.lib()
+    ws = torch.empty(L.dbx_resize_batch_workspace_bytes(len(spec)), dtype=torch.uint8, device=arena.device)
+    check(L.dbx_resize_cubic_batch_u8(jobs, len(spec), c, C.c_void_p(arena.data_ptr()), C.c_void_p(ws.data_ptr()), stream_ptr()))
+
+
 def _resize_jobs(dev, spec, c):
     """ONE launch over spec = [(b, cx0, cy0, cw, ch, pad_l, pad_t, pad_r, pad_b, dh, dw)], all with the same dh x dw: the uint8
     [len(spec), dh, dw, c] CUDA tensor of the jobs' results in order.  dev[b]: contiguous uint8 [H,W,c] CUDA tensors."""
     dh, dw = spec[0][9], spec[0][10]
     block = dh * dw * c            # the jobs' blocks back to back ARE the result: the kernel stores aligned words at any offset
-    device = dev[0].device
-    out = torch.empty((len(spec), dh, dw, c), dtype=torch.uint8, device=device)
-    jobs = (_lib.ResizeJob * len(spec))()
-    for i, (r, (b, cx0, cy0, cw, ch, pl, pt, pr, pb, jh, jw)) in enumerate(zip(jobs, spec)):
-        r.src = dev[b].data_ptr()
-        r.sh, r.sw = int(dev[b].size(0)), int(dev[b].size(1))
-        r.cx0, r.cy0, r.cw, r.ch = cx0, cy0, cw, ch
-        r.pad_l, r.pad_t, r.pad_r, r.pad_b, r.pad_value = pl, pt, pr, pb, PAD_VALUE
-        r.dh, r.dw, r.dst_off = jh, jw, i * block
-    L = _lib.lib()
-    ws = torch.empty(L.dbx_resize_batch_workspace_bytes(len(spec)), dtype=torch.uint8, device=device)
-    check(L.dbx_resize_cubic_batch_u8(jobs, len(spec), c, C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), stream_ptr()))
+    out = torch.empty((len(spec), dh, dw, c), dtype=torch.uint8, device=dev[0].device)
+    _launch_jobs(dev, spec, [i * block for i in range(len(spec))], c, out)
     return out
 
 
@@ -65,14 +70,44 @@ def _check_size(who, size):
     return int(w), int(h)
 
 
-def _pad_resize_device(dev, size):
-    """pad_resize_batch on images already on the device."""
+def _pad_spec(dev, size):
+    """pad_img + resize to size x size of every image of dev, as _resize_jobs' job tuples."""
     spec = []
     for b, im in enumerate(dev):
         h, w = int(im.size(0)), int(im.size(1))
         side, px, py = pad_geometry(h, w)
         spec.append((b, 0, 0, w, h, px, py, side - w - px, side - h - py, size, size))
-    return _resize_jobs(dev, spec, int(dev[0].size(2)))
+    return spec
+
+
+def _pad_resize_device(dev, size):
+    """pad_resize_batch on images already on the device."""
+    return _resize_jobs(dev, _pad_spec(dev, size), int(dev[0].size(2)))
+
+
+def _pad_resize_levels(dev, sizes):
+    """_pad_resize_device at every size of `sizes` in ONE launch of len(dev) * len(sizes) jobs: a list with one uint8
+    [B, size, size, C] CUDA tensor per size.  The tensors are views of one arena -- a level's jobs write back to back, so its block of
+    the arena IS that tensor -- and every job is the one _pad_resize_device builds for that size."""
+    c = int(dev[0].size(2))
+    spec, offs, starts, pos = [], [], [], 0
+    for size in sizes:
+        starts.append(pos)
+        for job in _pad_spec(dev, int(size)):
+            spec.append(job)
+            offs.append(pos)
+            pos += int(size) * int(size) * c
+    arena = torch.empty(pos, dtype=torch.uint8, device=dev[0].device)
+    _launch_jobs(dev, spec, offs, c, arena)
+    B = len(dev)
+    return [arena[st:st + B * int(sz) * int(sz) * c].view(B, int(sz), int(sz), c) for st, sz in zip(starts, sizes)]
+
+
+def level_xform(h, w, size):
+    """(scale, off_x, off_y) that maps coordinates in the size x size resize of pad_img of an h x w frame back to the frame:
+    x_src = x * scale - off_x, y_src = y * scale - off_y, with scale = side / size and the offsets pad_geometry's padding."""
+    side, pad_x, pad_y = pad_geometry(h, w)
+    return side / int(size), float(pad_x), float(pad_y)
 
 
 def pad_resize_batch(images, size=720):

@@ -49,8 +49,9 @@ const char* dbx_last_error(void);
  *      entry points accept DBX_F32 (reference instantiations for the parity suite)
  *   8  additions only: dbx_detect_batch, dbx_detect_batch_scratch_bytes (one decode + NMS launch over a batch of images)
  *   9  additions only: dbx_warp_job, dbx_warp_perspective_batch_u8, dbx_warp_batch_workspace_bytes (every plate of a batch in one launch)
- *  10  additions only: dbx_resize_job, dbx_resize_cubic_batch_u8, dbx_resize_batch_workspace_bytes (batched pad + bicubic resize) */
-#define DBX_ABI_VERSION 10
+ *  10  additions only: dbx_resize_job, dbx_resize_cubic_batch_u8, dbx_resize_batch_workspace_bytes (batched pad + bicubic resize)
+ *  11  additions only: dbx_merge_xform, dbx_merge_nms_batch, dbx_merge_nms_batch_workspace_bytes (pyramid levels merged + one NMS per frame) */
+#define DBX_ABI_VERSION 11
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
 int dbx_device_arch(int device);
@@ -443,6 +444,27 @@ int dbx_detect_batch(const float* score, const float* loc, const float* lm_heat,
                      double* dets, int32_t det_cols, int64_t* topk_idx, int32_t* keep, void* scratch, void* stream);
 /* scratch: 5*n bytes */
 int dbx_nms(const double* dets, int32_t n, int32_t det_cols, double nms_thresh, int32_t* keep, void* scratch, void* stream);
+
+/* ---- pyramid merge: the rows of `levels` runs of dbx_detect_batch over the same `batch` frames (each run on the frames resized to
+ * another size) mapped back to source-frame coordinates, and ONE greedy NMS per frame over their union -- one launch, one workgroup
+ * per frame.
+ * level_dets[l]: device rows [batch][K][det_cols] as dbx_detect_batch writes them.  xform[l * batch + b] maps level l's resized-frame
+ * coordinates of frame b back to its source frame: x_src = x * scale - off_x, y_src = y * scale - off_y in float64, the product
+ * rounded before the subtraction (no fused multiply-add): bit for bit NumPy's `d * scale - off`.
+ * out_dets [batch][levels * K][det_cols]: row l * K + r of frame b is row r of level l with the x columns (0, 2, and 5, 7, 9, 11 when
+ * det_cols == 13) and the y columns (1, 3, and 6, 8, 10, 12) mapped; column 4, the score, is copied; NaN rows pass through.
+ * out_keep [batch][levels * K + 1]: per frame what dbx_nms returns on out_dets[b] (keep[0] = count; kept row numbers of out_dets[b] in
+ * the reference's order; the level of a kept row is index / K) -- the same device code.
+ * level_dets and xform are HOST arrays: the library copies its device records into `workspace` (device,
+ * dbx_merge_nms_batch_workspace_bytes(levels, batch, K) bytes, which also holds every frame's NMS scratch) on `stream`, so the caller
+ * may reuse them when the call returns and must keep `workspace` until the launch has run.  Refused with DBX_ERR_ARG before anything
+ * is queued: levels, batch or K below 1, det_cols other than 5 or 13, a null pointer (any level pointer included), a scale that is not
+ * finite and positive, a non-finite offset, levels * K above 4096 rows per frame (the rank pass of the NMS is quadratic in the row
+ * count).  The workspace size is -1 for such counts. */
+typedef struct dbx_merge_xform { double scale, off_x, off_y; } dbx_merge_xform;
+int64_t dbx_merge_nms_batch_workspace_bytes(int32_t levels, int32_t batch, int32_t K);
+int dbx_merge_nms_batch(const double* const* level_dets, const dbx_merge_xform* xform, int32_t levels, int32_t batch, int32_t K,
+                        int32_t det_cols, double nms_thresh, double* out_dets, int32_t* out_keep, void* workspace, void* stream);
 
 /* ---- plate rectification after decode (perspective_transform, DenseBox.py:3446-3481; OpenCV's published algorithm) ----
  * dbx_perspective_matrix: host function, cv2.getPerspectiveTransform: 3x3 row-major double map src -> dst of four (x, y)
