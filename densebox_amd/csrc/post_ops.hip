@@ -263,6 +263,87 @@ __device__ __forceinline__ unsigned det_key(float v) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// One decoded row d[dc] of pixel idx of an n = rows x cols map: the row writer of every decode kernel (top-K and threshold), so they
+// cannot drift apart.  lm_loc: parse_DetLMLOC's eight offsets; else (dc == 13) lm_arg[4], parse_DetLM's shared heat-map arg-max.
+__device__ __forceinline__ void det_write_row(double* d, int idx, const float* score, const float* loc, const float* lm_loc,
+                                              const int* lm_arg, int n, int cols, int dc) {
+    const float xi = (float)(idx % cols), yi = (float)(idx / cols);
+    // fp32 subtraction (python int - fp32 tensor), then float()*4.0 in double (DenseBox.py:3334-3343)
+    d[0] = (double)(xi - loc[idx]) * 4.0;
+    d[1] = (double)(yi - loc[(size_t)n + idx]) * 4.0;
+    d[2] = (double)(xi - loc[(size_t)2 * n + idx]) * 4.0;
+    d[3] = (double)(yi - loc[(size_t)3 * n + idx]) * 4.0;
+    d[4] = (double)score[idx];
+    if (dc == 13) {
+        if (lm_loc) {
+            for (int c = 0; c < 8; ++c)
+                d[5 + c] = (double)(((c & 1) ? yi : xi) - lm_loc[(size_t)c * n + idx]) * 4.0;   // :3183-3196
+        } else {
+            for (int j = 0; j < 4; ++j) {
+                d[5 + 2 * j] = (double)(float)(lm_arg[j] % cols) * 4.0;
+                d[6 + 2 * j] = (double)(float)(lm_arg[j] / cols) * 4.0;
+            }
+        }
+    }
+}
+
+// Radix select of the K largest scores of score[0..n) (four 8-bit passes over det_key, LDS histogram `hist` [256]), then compaction of the
+// keys above the K-th plus the lowest-index ties: exactly K (key << 32 | ~index) composites in cand[0..K), in no particular order.
+// Every thread of a DET_THREADS-wide workgroup calls it; it returns behind a barrier.
+__device__ __forceinline__ void det_radix_select(const float* score, int n, int K, unsigned* hist, unsigned long long* cand) {
+    const int tid = threadIdx.x;
+    __shared__ unsigned sel_prefix, sel_remaining, sel_ties, cand_n, tie_base[DET_THREADS / 64 + 1];
+    if (tid == 0) { sel_prefix = 0; sel_remaining = (unsigned)K; }
+    __syncthreads();
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        const unsigned prefix = sel_prefix;
+        for (int i = tid; i < n; i += DET_THREADS) {
+            const unsigned k = det_key(score[i]);
+            if (pass == 0 || (k >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(k >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned rem = sel_remaining, b = 255;
+            for (;; --b) { const unsigned c = hist[b]; if (c >= rem || b == 0) break; rem -= c; }
+            sel_prefix = prefix | (b << shift); sel_remaining = rem; sel_ties = hist[b];
+        }
+        __syncthreads();
+    }
+    const unsigned T = sel_prefix, need = sel_remaining, ties = sel_ties;     // K-th key; how many of its `ties` copies are taken
+    if (tid == 0) cand_n = 0;
+    __syncthreads();
+    for (int i = tid; i < n; i += DET_THREADS) {
+        const unsigned k = det_key(score[i]);
+        if (k > T || (k == T && ties == need)) {
+            const unsigned slot = atomicAdd(&cand_n, 1u);
+            cand[slot] = ((unsigned long long)k << 32) | (unsigned)(~(unsigned)i);
+        }
+    }
+    __syncthreads();
+    if (ties != need) {
+        // more copies of the K-th score than places: the lowest indices win.  Thread t owns the contiguous index range
+        // [t * seg, (t + 1) * seg): per-thread tie counts -> exclusive block scan -> the first `need` ties in index order.
+        const int seg = (n + DET_THREADS - 1) / DET_THREADS, lo = tid * seg, hi = min(n, lo + seg);
+        unsigned mine = 0;
+        for (int i = lo; i < hi; ++i) mine += det_key(score[i]) == T;
+        unsigned incl = mine;                                   // inclusive scan inside the wave
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { const unsigned o = __shfl_up(incl, off); if ((tid & 63) >= off) incl += o; }
+        if ((tid & 63) == 63) tie_base[(tid >> 6) + 1] = incl;
+        __syncthreads();
+        if (tid == 0) { tie_base[0] = 0; for (int w = 1; w <= DET_THREADS / 64; ++w) tie_base[w] += tie_base[w - 1]; }
+        __syncthreads();
+        unsigned before = tie_base[tid >> 6] + incl - mine;
+        const unsigned base_slot = cand_n;
+        for (int i = lo; i < hi && before < need; ++i)
+            if (det_key(score[i]) == T) { cand[base_slot + before] = ((unsigned long long)T << 32) | (unsigned)(~(unsigned)i); ++before; }
+        __syncthreads();
+    }
+}
+
 // top-K by radix select + sort from this K on; below it the arg-max rounds over the two-level LDS structure are faster (same-box
 // A/B at K = 10 on a 128 x 128 map: whole 512 x 512 detect() 0.486 ms with rounds, 0.506 ms with select + a 16-element sort).
 #ifndef DET_SELECT_MIN_K
@@ -359,56 +440,7 @@ __global__ __launch_bounds__(DET_THREADS) void detect_kernel(const DetArgs a0) {
         // (key, index) pairs in LDS -- ~0.1 ms, the same ranking bit for bit.
         unsigned* hist = (unsigned*)bmax;                        // [256]
         unsigned long long* cand = (unsigned long long*)bidx;    // [1024] (key << 32) | ~index: descending sort = reference order
-        __shared__ unsigned sel_prefix, sel_remaining, sel_ties, cand_n, tie_base[DET_THREADS / 64 + 1];
-        if (tid == 0) { sel_prefix = 0; sel_remaining = (unsigned)a.K; }
-        __syncthreads();
-        for (int pass = 0; pass < 4; ++pass) {
-            const int shift = 24 - 8 * pass;
-            if (tid < 256) hist[tid] = 0;
-            __syncthreads();
-            const unsigned prefix = sel_prefix;
-            for (int i = tid; i < n; i += DET_THREADS) {
-                const unsigned k = det_key(a.score[i]);
-                if (pass == 0 || (k >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(k >> shift) & 255u], 1u);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                unsigned rem = sel_remaining, b = 255;
-                for (;; --b) { const unsigned c = hist[b]; if (c >= rem || b == 0) break; rem -= c; }
-                sel_prefix = prefix | (b << shift); sel_remaining = rem; sel_ties = hist[b];
-            }
-            __syncthreads();
-        }
-        const unsigned T = sel_prefix, need = sel_remaining, ties = sel_ties;     // K-th key; how many of its `ties` copies are taken
-        if (tid == 0) cand_n = 0;
-        __syncthreads();
-        for (int i = tid; i < n; i += DET_THREADS) {
-            const unsigned k = det_key(a.score[i]);
-            if (k > T || (k == T && ties == need)) {
-                const unsigned slot = atomicAdd(&cand_n, 1u);
-                cand[slot] = ((unsigned long long)k << 32) | (unsigned)(~(unsigned)i);
-            }
-        }
-        __syncthreads();
-        if (ties != need) {
-            // more copies of the K-th score than places: the lowest indices win.  Thread t owns the contiguous index range
-            // [t * seg, (t + 1) * seg): per-thread tie counts -> exclusive block scan -> the first `need` ties in index order.
-            const int seg = (n + DET_THREADS - 1) / DET_THREADS, lo = tid * seg, hi = min(n, lo + seg);
-            unsigned mine = 0;
-            for (int i = lo; i < hi; ++i) mine += det_key(a.score[i]) == T;
-            unsigned incl = mine;                                   // inclusive scan inside the wave
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) { const unsigned o = __shfl_up(incl, off); if ((tid & 63) >= off) incl += o; }
-            if ((tid & 63) == 63) tie_base[(tid >> 6) + 1] = incl;
-            __syncthreads();
-            if (tid == 0) { tie_base[0] = 0; for (int w = 1; w <= DET_THREADS / 64; ++w) tie_base[w] += tie_base[w - 1]; }
-            __syncthreads();
-            unsigned before = tie_base[tid >> 6] + incl - mine;
-            const unsigned base_slot = cand_n;
-            for (int i = lo; i < hi && before < need; ++i)
-                if (det_key(a.score[i]) == T) { cand[base_slot + before] = ((unsigned long long)T << 32) | (unsigned)(~(unsigned)i); ++before; }
-            __syncthreads();
-        }
+        det_radix_select(a.score, n, a.K, hist, cand);
         int P2 = 2;                                               // sort size: the power of two >= K (K = 10: 16 elements, 10 exchange steps)
         while (P2 < a.K) P2 <<= 1;
         for (int i = a.K + tid; i < P2; i += DET_THREADS) cand[i] = 0ull;                // padding sorts last
@@ -493,26 +525,7 @@ __global__ __launch_bounds__(DET_THREADS) void detect_kernel(const DetArgs a0) {
     __syncthreads();
     // ---- decode: one thread per detection (the rows no longer sit as dependent global loads inside the selection rounds)
     for (int k = tid; k < a.K; k += DET_THREADS) {
-        const int idx = (int)a.topk[k];
-        const float xi = (float)(idx % a.cols), yi = (float)(idx / a.cols);
-        double* d = a.dets + (size_t)k * a.dc;
-        // fp32 subtraction (python int - fp32 tensor), then float()*4.0 in double (DenseBox.py:3334-3343)
-        d[0] = (double)(xi - a.loc[idx]) * 4.0;
-        d[1] = (double)(yi - a.loc[(size_t)n + idx]) * 4.0;
-        d[2] = (double)(xi - a.loc[(size_t)2 * n + idx]) * 4.0;
-        d[3] = (double)(yi - a.loc[(size_t)3 * n + idx]) * 4.0;
-        d[4] = (double)a.score[idx];
-        if (a.dc == 13) {
-            if (a.lm_loc) {
-                for (int c = 0; c < 8; ++c)
-                    d[5 + c] = (double)(((c & 1) ? yi : xi) - a.lm_loc[(size_t)c * n + idx]) * 4.0;   // :3183-3196
-            } else {
-                for (int j = 0; j < 4; ++j) {
-                    d[5 + 2 * j] = (double)(float)(lm_arg[j] % a.cols) * 4.0;
-                    d[6 + 2 * j] = (double)(float)(lm_arg[j] / a.cols) * 4.0;
-                }
-            }
-        }
+        det_write_row(a.dets + (size_t)k * a.dc, (int)a.topk[k], a.score, a.loc, a.lm_loc, lm_arg, n, a.cols, a.dc);
     }
     __threadfence_block();
     __syncthreads();
@@ -665,6 +678,329 @@ extern "C" int dbx_merge_nms_batch(const double* const* level_dets, const dbx_me
     hipLaunchKernelGGL(merge_nms_kernel, dim3(batch), dim3(DET_THREADS), 0, (hipStream_t)stream, (const double* const*)ws,
                        (const dbx_merge_xform*)(ws + (size_t)levels * 8), levels, batch, K, det_cols, nms_thresh, out_dets, out_keep,
                        ws + head, (long long)merge_slice_bytes((int64_t)levels * K));
+    DBX_LAUNCH_CHECK();
+    return DBX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- threshold decode + NMS for <= 4096 rows
+// dbx_detect_thresh_batch: per image every pixel with score > t (strict: NaN never, +inf always, -0.0 > 0.0 is false) is a candidate row,
+// at most `cap` of them (the best in the top-K order when more pass), and the reference's greedy NMS runs over all of them.  Three
+// launches whose grids depend on (batch, cap) alone -- the counts stay on the device, so the sequence can be captured:
+//   1. thresh_select_kernel, one workgroup per image: ONE pass over the map counts and compacts the (det_key << 32 | ~index) composites
+//      into LDS (the radix select runs only when more than cap pass), a bitonic sort puts them into the reference's row order, the rows
+//      go to the image's scratch slice through det_write_row, and the NMS order comes from the sort (runs of equal scores reversed:
+//      nms_block ranks the HIGHER row index first on ties) -- no quadratic rank pass.  counts[b] = (n_b, pixels above t).
+//   2. thresh_pack_mask_kernel, grid (cap / 64, batch): workgroup (rb, b) copies rows [64 rb, 64 rb + 64) of image b behind the rows of
+//      the images before it (exclusive prefix of the counts) and fills those rows of the suppression matrix, every word at or right of
+//      the diagonal, with nms_block's fp64 expression; workgroups past n_b leave at once.  Many CUs per image.
+//   3. thresh_sweep_kernel, one wave per image: the greedy walk with the removed set in registers (lane w holds word w of 64).
+// dbx_nms_large runs 2 (without the copy) and 3 on caller rows behind a sort of (score key, row index) pairs.
+#define THR_MAX_DETS 4096
+#define NMSL_THREADS 256
+
+static __host__ __device__ inline long long thr_up256(long long v) { return (v + 255) / 256 * 256; }
+// one image's scratch slice: rows [cap][13] float64 | map indices [cap] int64 | NMS order [cap] int32 | matrix [cap][ceil(cap / 64)] words
+struct ThrLayout { long long topk, order, mask, total; int nw; };
+static __host__ __device__ inline ThrLayout thr_layout(int cap) {
+    ThrLayout L;
+    L.nw = (cap + 63) / 64;
+    L.topk = thr_up256((long long)cap * 13 * 8);
+    L.order = L.topk + thr_up256((long long)cap * 8);
+    L.mask = L.order + thr_up256((long long)cap * 4);
+    L.total = L.mask + thr_up256((long long)cap * L.nw * 8);
+    return L;
+}
+
+struct ThrArgs {
+    const float* score; const float* loc; const float* lm_heat; const float* lm_loc;
+    int batch, rows, cols, dc, cap, keep_behind_rows;
+    float t; double thresh;
+    double* dets; long long* topk; int* keep; int* counts;        // counts: [batch][2] pairs, then the [batch + 1] exclusive prefix
+    unsigned char* scratch;
+};
+
+// descending bitonic sort of a[0..P2) in LDS by the whole workgroup (a barrier in front is the caller's)
+__device__ __forceinline__ void bitonic_desc_u64(unsigned long long* a, int P2) {
+    for (int size = 2; size <= P2; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < (P2 >> 1); t += blockDim.x) {
+                const int i = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), j = i | stride;
+                const unsigned long long x = a[i], y = a[j];
+                if (((i & size) == 0) ? x < y : x > y) { a[i] = y; a[j] = x; }
+            }
+            __syncthreads();
+        }
+}
+
+__global__ __launch_bounds__(DET_THREADS) void thresh_select_kernel(const ThrArgs a) {
+    const size_t b = blockIdx.x;
+    const int tid = threadIdx.x, n = a.rows * a.cols, cap = a.cap;
+    const float* score = a.score + b * (size_t)n;
+    const float* loc = a.loc + b * 4 * (size_t)n;
+    const float* lm_heat = a.lm_heat ? a.lm_heat + b * 4 * (size_t)n : nullptr;
+    const float* lm_loc = a.lm_loc ? a.lm_loc + b * 8 * (size_t)n : nullptr;
+    const ThrLayout L = thr_layout(cap);
+    unsigned char* const s = a.scratch + b * (size_t)L.total;
+    double* const rows_fs = (double*)s;
+    long long* const topk_fs = (long long*)(s + L.topk);
+    int* const order = (int*)(s + L.order);
+    __shared__ float red_v[DET_THREADS / 64];
+    __shared__ int red_i[DET_THREADS / 64];
+    __shared__ int lm_arg[4];
+    __shared__ unsigned long long cand[THR_MAX_DETS];
+    __shared__ unsigned hist[256];
+    __shared__ unsigned above;
+    if (tid < 4) lm_arg[tid] = 0;
+    if (tid == 0) above = 0;
+    __syncthreads();
+    if (lm_heat && !lm_loc) {
+        for (int j = 0; j < 4; ++j) {
+            float v; int idx;
+            block_argmax_g(lm_heat + (size_t)j * n, n, red_v, red_i, v, idx);
+            if (tid == 0) lm_arg[j] = idx;
+        }
+        __syncthreads();
+    }
+    // ---- threshold + compaction in one pass; slots past the cap are counted, not stored
+    for (int i = tid; i < n; i += DET_THREADS) {
+        const float v = score[i];
+        if (v > a.t) {
+            const unsigned slot = atomicAdd(&above, 1u);
+            if (slot < (unsigned)cap) cand[slot] = ((unsigned long long)det_key(v) << 32) | (unsigned)(~(unsigned)i);
+        }
+    }
+    __syncthreads();
+    const unsigned total = above;
+    const int nb = total < (unsigned)cap ? (int)total : cap;
+    if (total > (unsigned)cap) det_radix_select(score, n, cap, hist, cand);          // the cap best of the map = the cap best candidates
+    int P2 = 2;
+    while (P2 < nb) P2 <<= 1;
+    for (int i = nb + tid; i < P2; i += DET_THREADS) cand[i] = 0ull;                    // padding sorts last
+    __syncthreads();
+    bitonic_desc_u64(cand, P2);
+    // ---- rows in the reference's order; NMS position of row r of a run [s, e) of equal scores: s + (e - 1 - r)
+    for (int r = tid; r < nb; r += DET_THREADS) {
+        const unsigned long long c = cand[r];
+        const unsigned key = (unsigned)(c >> 32);
+        const int idx = (int)(~(unsigned)(c & 0xffffffffull));
+        det_write_row(rows_fs + (size_t)r * a.dc, idx, score, loc, lm_loc, lm_arg, n, a.cols, a.dc);
+        topk_fs[r] = idx;
+        int lo = 0, hi = r;                                         // first position whose key is <= key
+        while (lo < hi) { const int m = (lo + hi) >> 1; if ((unsigned)(cand[m] >> 32) > key) lo = m + 1; else hi = m; }
+        const int rs = lo;
+        lo = r + 1; hi = nb;                                        // first position whose key is < key
+        while (lo < hi) { const int m = (lo + hi) >> 1; if ((unsigned)(cand[m] >> 32) >= key) lo = m + 1; else hi = m; }
+        order[rs + (lo - 1 - r)] = r;
+    }
+    if (tid == 0) { a.counts[2 * b] = nb; a.counts[2 * b + 1] = (int)total; }
+}
+
+// Rows [64 rb, 64 rb + 64) (in NMS order: position p is row order[p] of dets) of the n x nw suppression matrix, the words at or right of
+// the diagonal: bit q of row p (q > p) = box p suppresses box q, nms_block's expression.  Words left of the diagonal are never written
+// and never read.  NMSL_THREADS threads: lane = row, the four waves share the words; a wave stages the 64 column boxes of its word
+// in LDS (10 KB in all) and every lane reads them back as broadcasts.
+__device__ __forceinline__ void nmsl_mask_rows(const double* dets, int dc, const int* order, int n, double thresh,
+                                               unsigned long long* mask, int nw_stride, int rb) {
+    __shared__ double cb[NMSL_THREADS / 64][5][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int p = rb * 64 + lane, nw = (n + 63) >> 6;
+    double x1 = 0, y1 = 0, x2 = 0, y2 = 0, ai = 0;
+    if (p < n) {
+        const double* d = dets + (size_t)order[p] * dc;
+        x1 = d[0]; y1 = d[1]; x2 = d[2]; y2 = d[3];
+        ai = (x2 - x1 + 1) * (y2 - y1 + 1);
+    }
+    for (int w0 = rb; w0 < nw; w0 += NMSL_THREADS / 64) {            // (uniform trip count: the barriers are reached by every wave)
+        const int w = w0 + wv, q0 = 64 * w + lane;
+        if (q0 < n) {
+            const double* d = dets + (size_t)order[q0] * dc;
+            const double u1 = d[0], v1 = d[1], u2 = d[2], v2 = d[3];
+            cb[wv][0][lane] = u1; cb[wv][1][lane] = v1; cb[wv][2][lane] = u2; cb[wv][3][lane] = v2;
+            cb[wv][4][lane] = (u2 - u1 + 1) * (v2 - v1 + 1);
+        }
+        __syncthreads();
+        if (w < nw && p < n) {
+            unsigned long long bits = 0ull;
+            const int cn = min(64, n - 64 * w);
+            for (int c = 0; c < cn; ++c) {
+                if (64 * w + c <= p) continue;
+                const double xx1 = fmax(x1, cb[wv][0][c]), yy1 = fmax(y1, cb[wv][1][c]), xx2 = fmin(x2, cb[wv][2][c]), yy2 = fmin(y2, cb[wv][3][c]);
+                const double ww = fmax(0.0, xx2 - xx1 + 1), hh = fmax(0.0, yy2 - yy1 + 1);
+                const double inter = ww * hh;
+                const double ovr = inter / (ai + cb[wv][4][c] - inter);
+                if (!(ovr <= thresh)) bits |= 1ull << c;             // NaN is dropped, like np.where(ovr <= t)
+            }
+            mask[(size_t)p * nw_stride + w] = bits;
+        }
+        __syncthreads();
+    }
+}
+
+// The greedy walk by ONE wave: lane w holds word w of the removed set, the matrix rows come in blocks of 32 with the next block's loads
+// in flight while this one is walked.  keep[0] = count, keep[1..] = kept rows in NMS order.
+__device__ __forceinline__ void nmsl_sweep(const unsigned long long* mask, int nw_stride, const int* order, int n, int* keep) {
+    const int lane = threadIdx.x & 63, nw = (n + 63) >> 6;
+    unsigned long long removed = 0ull, cur[32], nxt[32];
+    int cnt = 0, ord_c = 0, ord_n = 0;
+#pragma unroll
+    for (int r = 0; r < 32; ++r) cur[r] = (lane < nw && r < n) ? mask[(size_t)r * nw_stride + lane] : 0ull;
+    if (lane < 32 && lane < n) ord_c = order[lane];
+    for (int p0 = 0; p0 < n; p0 += 32) {
+        const int p1 = p0 + 32;
+#pragma unroll
+        for (int r = 0; r < 32; ++r) nxt[r] = (lane < nw && lane >= (p1 >> 6) && p1 + r < n) ? mask[(size_t)(p1 + r) * nw_stride + lane] : 0ull;
+        ord_n = (lane < 32 && p1 + lane < n) ? order[p1 + lane] : 0;
+#pragma unroll
+        for (int r = 0; r < 32; ++r) {
+            const int pos = p0 + r;
+            if (pos < n) {
+                const unsigned long long word = __shfl(removed, pos >> 6);
+                if (!((word >> (pos & 63)) & 1ull)) {              // (uniform) box `pos` survives
+                    const int row = __shfl(ord_c, r);
+                    if (lane == 0) keep[1 + cnt] = row;
+                    ++cnt;
+                    removed |= cur[r];
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 32; ++r) cur[r] = nxt[r];
+        ord_c = ord_n;
+    }
+    if (lane == 0) keep[0] = cnt;
+}
+
+__global__ __launch_bounds__(NMSL_THREADS) void thresh_pack_mask_kernel(const ThrArgs a) {
+    const int rb = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int n = a.counts[2 * b];
+    if (rb > 0 && 64 * rb >= n) return;
+    __shared__ int s_pre, s_tot;
+    if (tid == 0) { s_pre = 0; s_tot = 0; }
+    __syncthreads();
+    int pre = 0, tot = 0;
+    for (int j = tid; j < a.batch; j += NMSL_THREADS) { const int c = a.counts[2 * j]; tot += c; pre += j < b ? c : 0; }
+    atomicAdd(&s_pre, pre); atomicAdd(&s_tot, tot);
+    __syncthreads();
+    pre = s_pre; tot = s_tot;
+    int* const prefix = a.counts + 2 * (size_t)a.batch;
+    if (rb == 0 && tid == 0) { prefix[b] = pre; if (b == a.batch - 1) prefix[a.batch] = tot; }
+    if (64 * rb >= n) return;
+    const ThrLayout L = thr_layout(a.cap);
+    unsigned char* const s = a.scratch + (size_t)b * L.total;
+    const double* rows_fs = (const double*)s;
+    const long long* topk_fs = (const long long*)(s + L.topk);
+    const int r0 = 64 * rb, nr = min(64, n - r0);
+    double* const od = a.dets + ((size_t)pre + r0) * a.dc;
+    for (int e = tid; e < nr * a.dc; e += NMSL_THREADS) od[e] = rows_fs[(size_t)r0 * a.dc + e];
+    for (int r = tid; r < nr; r += NMSL_THREADS) a.topk[(size_t)pre + r0 + r] = topk_fs[r0 + r];
+    nmsl_mask_rows(rows_fs, a.dc, (const int*)(s + L.order), n, a.thresh, (unsigned long long*)(s + L.mask), L.nw, rb);
+}
+
+__global__ __launch_bounds__(64) void thresh_sweep_kernel(const ThrArgs a) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    int pre = 0, tot = 0;
+    for (int j = lane; j < a.batch; j += 64) { const int c = a.counts[2 * j]; tot += c; pre += j < b ? c : 0; }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { pre += __shfl_xor(pre, off); tot += __shfl_xor(tot, off); }
+    // image b's keep list: n_b + 1 words behind those of the images before it; the lists start right behind the packed rows when asked
+    int* const keep = (a.keep_behind_rows ? (int*)(a.dets + (size_t)tot * a.dc) : a.keep) + (size_t)pre + b;
+    const ThrLayout L = thr_layout(a.cap);
+    const unsigned char* s = a.scratch + (size_t)b * L.total;
+    nmsl_sweep((const unsigned long long*)(s + L.mask), L.nw, (const int*)(s + L.order), a.counts[2 * b], keep);
+}
+
+extern "C" int64_t dbx_detect_thresh_batch_scratch_bytes(int32_t batch, int32_t rows, int32_t cols, int32_t max_dets) {
+    if (batch < 1 || rows < 1 || cols < 1 || max_dets < 1 || max_dets > THR_MAX_DETS) return -1;
+    return (int64_t)batch * thr_layout(max_dets).total;
+}
+
+extern "C" int dbx_detect_thresh_batch(const float* score, const float* loc, const float* lm_heat, const float* lm_loc, int32_t batch,
+                                       int32_t rows, int32_t cols, float score_thresh, int32_t max_dets, double nms_thresh, double* dets,
+                                       int32_t det_cols, int64_t* topk_idx, int32_t* keep, int32_t* counts, void* scratch, void* stream) {
+    DBX_REQUIRE(score && loc && dets && topk_idx && keep && counts && scratch, "detect_thresh_batch: null argument");
+    DBX_REQUIRE(batch > 0, "detect_thresh_batch: batch=%d must be positive", batch);
+    DBX_REQUIRE(rows > 0 && cols > 0 && (int64_t)rows * cols <= 0x7fffffff, "detect_thresh_batch: bad map size %d x %d", rows, cols);
+    DBX_REQUIRE(max_dets >= 1 && max_dets <= THR_MAX_DETS, "detect_thresh_batch: max_dets=%d must be 1..%d", max_dets, THR_MAX_DETS);
+    DBX_REQUIRE(!std::isnan(score_thresh), "detect_thresh_batch: score_thresh is NaN");
+    DBX_REQUIRE(!std::isnan(nms_thresh) && nms_thresh >= 0.0, "detect_thresh_batch: nms_thresh=%g must be a number >= 0", nms_thresh);
+    DBX_REQUIRE(det_cols == 5 || (det_cols == 13 && (lm_heat || lm_loc)), "detect_thresh_batch: det_cols must be 5, or 13 with landmark maps");
+    DBX_REQUIRE((int64_t)batch * max_dets <= 0x7fffffff / 16, "detect_thresh_batch: batch * max_dets = %lld rows do not fit the packed arena's int32 prefix",
+                (long long)batch * max_dets);
+    ThrArgs a;
+    a.score = score; a.loc = loc; a.lm_heat = lm_heat; a.lm_loc = lm_loc;
+    a.batch = batch; a.rows = rows; a.cols = cols; a.dc = det_cols; a.cap = max_dets;
+    a.keep_behind_rows = (const void*)keep == (const void*)dets;
+    a.t = score_thresh; a.thresh = nms_thresh;
+    a.dets = dets; a.topk = (long long*)topk_idx; a.keep = keep; a.counts = counts; a.scratch = (unsigned char*)scratch;
+    hipLaunchKernelGGL(thresh_select_kernel, dim3(batch), dim3(DET_THREADS), 0, (hipStream_t)stream, a);
+    DBX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(thresh_pack_mask_kernel, dim3((max_dets + 63) / 64, batch), dim3(NMSL_THREADS), 0, (hipStream_t)stream, a);
+    DBX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(thresh_sweep_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, a);
+    DBX_LAUNCH_CHECK();
+    return DBX_OK;
+}
+
+// ---- dbx_nms_large: the same matrix + sweep on caller rows.  The order comes from a bitonic sort of (score key, row) pairs in LDS
+// (48 KB): key = the float64 score's bits made order-preserving, -0 == +0, every NaN the largest; larger key first, the higher row first
+// among equal keys -- nms_block's rank for every input.
+__global__ __launch_bounds__(DET_THREADS) void nms_large_order_kernel(const double* dets, int n, int dc, int* order) {
+    __shared__ unsigned long long key[THR_MAX_DETS];
+    __shared__ int row[THR_MAX_DETS];
+    int P2 = 2;
+    while (P2 < n) P2 <<= 1;
+    for (int i = threadIdx.x; i < P2; i += DET_THREADS) {
+        unsigned long long k = 0ull;                                 // padding: below -inf's key
+        if (i < n) {
+            const double sc = dets[(size_t)i * dc + 4];
+            if (sc != sc) k = ~0ull;
+            else if (sc == 0.0) k = 0x8000000000000000ull;
+            else { const unsigned long long u = (unsigned long long)__double_as_longlong(sc); k = (u >> 63) ? ~u : (u | 0x8000000000000000ull); }
+        }
+        key[i] = k; row[i] = i < n ? i : -1;
+    }
+    __syncthreads();
+    for (int size = 2; size <= P2; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < (P2 >> 1); t += DET_THREADS) {
+                const int i = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), j = i | stride;
+                const unsigned long long x = key[i], y = key[j];
+                const int ri = row[i], rj = row[j];
+                const bool i_less = x < y || (x == y && ri < rj);
+                if (((i & size) == 0) == i_less) { key[i] = y; key[j] = x; row[i] = rj; row[j] = ri; }
+            }
+            __syncthreads();
+        }
+    for (int i = threadIdx.x; i < n; i += DET_THREADS) order[i] = row[i];
+}
+__global__ __launch_bounds__(NMSL_THREADS) void nms_large_mask_kernel(const double* dets, int n, int dc, double thresh, const int* order,
+                                                                      unsigned long long* mask) {
+    nmsl_mask_rows(dets, dc, order, n, thresh, mask, (n + 63) >> 6, blockIdx.x);
+}
+__global__ __launch_bounds__(64) void nms_large_sweep_kernel(const unsigned long long* mask, const int* order, int n, int* keep) {
+    nmsl_sweep(mask, (n + 63) >> 6, order, n, keep);
+}
+
+extern "C" int64_t dbx_nms_large_scratch_bytes(int32_t n) {
+    if (n < 1 || n > THR_MAX_DETS) return -1;
+    return thr_up256((long long)n * 4) + thr_up256((long long)n * ((n + 63) / 64) * 8);
+}
+
+extern "C" int dbx_nms_large(const double* dets, int32_t n, int32_t det_cols, double nms_thresh, int32_t* keep, void* scratch,
+                             void* stream) {
+    DBX_REQUIRE(dets && keep && scratch, "nms_large: null argument");
+    DBX_REQUIRE(n >= 1 && n <= THR_MAX_DETS, "nms_large: n=%d must be 1..%d", n, THR_MAX_DETS);
+    DBX_REQUIRE(det_cols >= 5, "nms_large: det_cols=%d must be at least 5", det_cols);
+    DBX_REQUIRE(!std::isnan(nms_thresh) && nms_thresh >= 0.0, "nms_large: nms_thresh=%g must be a number >= 0", nms_thresh);
+    int* order = (int*)scratch;
+    unsigned long long* mask = (unsigned long long*)((unsigned char*)scratch + thr_up256((long long)n * 4));
+    hipLaunchKernelGGL(nms_large_order_kernel, dim3(1), dim3(DET_THREADS), 0, (hipStream_t)stream, dets, n, det_cols, order);
+    DBX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nms_large_mask_kernel, dim3((n + 63) / 64), dim3(NMSL_THREADS), 0, (hipStream_t)stream, dets, n, det_cols, nms_thresh,
+                       (const int*)order, mask);
+    DBX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nms_large_sweep_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const unsigned long long*)mask, (const int*)order, n,
+                       keep);
     DBX_LAUNCH_CHECK();
     return DBX_OK;
 }

@@ -122,7 +122,11 @@ def _graph_replay(net, tag, image, K, nms_thresh, eager, to_host=True):
     re-captured when the weight signature changes, at most _MAX_GRAPHS entries (LRU).
 
     to_host=False (detect_pyramid's 'level' entries): nothing is copied and nothing waits -- the replay is queued and the entry's
-    own device (dets, keep) are returned, valid in stream order until the entry's next replay."""
+    own device (dets, keep) are returned, valid in stream order until the entry's next replay.
+
+    to_host='second' (detect_batch_thresh's entries, K = (max_dets, score_thresh)): only the second result, the counts, is copied
+    by the graph; the first, the packed arena, is returned as the entry's device tensor -- how much of it to fetch depends on the
+    counts, and a copy of a size that depends on device data cannot be a graph node."""
     import collections
     cache = net.__dict__.setdefault('_detect_graphs', collections.OrderedDict())
     # weight signature: versions + storage addresses of every parameter (a replay reads the packed copies made at capture).
@@ -146,7 +150,8 @@ def _graph_replay(net, tag, image, K, nms_thresh, eager, to_host=True):
             wd, wk = eager(net, static_in, K, nms_thresh)
         h_dets = h_keep = None
         if to_host:
-            h_dets = torch.empty(wd.shape, dtype=wd.dtype).pin_memory()        # (pinned allocation is not capturable)
+            if to_host != 'second':
+                h_dets = torch.empty(wd.shape, dtype=wd.dtype).pin_memory()    # (pinned allocation is not capturable)
             h_keep = torch.empty(wk.shape, dtype=wk.dtype).pin_memory()
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
@@ -163,7 +168,8 @@ def _graph_replay(net, tag, image, K, nms_thresh, eager, to_host=True):
                 # the two result copies are graph nodes too (pinned destinations): one replay + one stream sync per call
                 # instead of two blocking .cpu() calls with their launch round trips (~60 us of idle GPU per call)
                 if to_host:
-                    h_dets.copy_(dets, non_blocking=True)
+                    if h_dets is not None:
+                        h_dets.copy_(dets, non_blocking=True)
                     h_keep.copy_(keep, non_blocking=True)
         finally:
             if gc_was_on:
@@ -182,7 +188,7 @@ def _graph_replay(net, tag, image, K, nms_thresh, eager, to_host=True):
     if not to_host:
         return dets, keep
     torch.cuda.current_stream().synchronize()
-    return h_dets, h_keep
+    return (dets if h_dets is None else h_dets), h_keep
 
 
 def detect(net, image, K=10, nms_thresh=0.4):
@@ -205,15 +211,15 @@ def detect(net, image, K=10, nms_thresh=0.4):
     return dets.cpu().numpy(), [int(v) for v in k[1:1 + int(k[0])]]
 
 
-def _batch_of(x, what):
+def _batch_of(x, what, fn='detect_batch'):
     """A 4-d network input from one tensor of `what`: float [B,3,H,W] or uint8 [B,H,W,3]."""
     if not torch.is_tensor(x):
-        raise RuntimeError('detect_batch: %s must be a tensor, got %s' % (what, type(x).__name__))
+        raise RuntimeError('%s: %s must be a tensor, got %s' % (fn, what, type(x).__name__))
     if x.dtype == torch.uint8:
         if x.dim() != 4 or x.size(3) != 3:
-            raise RuntimeError('detect_batch: uint8 %s must be [B,H,W,3] (HWC, RGB), got %s' % (what, list(x.shape)))
+            raise RuntimeError('%s: uint8 %s must be [B,H,W,3] (HWC, RGB), got %s' % (fn, what, list(x.shape)))
     elif not x.is_floating_point() or x.dim() != 4 or x.size(1) != 3:
-        raise RuntimeError('detect_batch: %s must be float [B,3,H,W] or uint8 [B,H,W,3], got %s %s' % (what, x.dtype, list(x.shape)))
+        raise RuntimeError('%s: %s must be float [B,3,H,W] or uint8 [B,H,W,3], got %s %s' % (fn, what, x.dtype, list(x.shape)))
     return x
 
 
@@ -239,27 +245,33 @@ def detect_batch(net, images, K=10, nms_thresh=0.4, max_batch=32):
     loop's directory walk).  List images are grouped by (shape, dtype) and never padded into one forward: padding would change
     the border activations after the first pooling and the bilinear up-sampling.  Eval mode replays a hipGraph per (batch
     shape, dtype, K, threshold, compute dtype) from the cache detect() uses; train mode and DBX_GRAPH=0 run eagerly."""
+    return _detect_many('detect_batch', images, max_batch, lambda x: _detect_chunk(net, x, K, nms_thresh))
+
+
+def _detect_many(fn, images, max_batch, chunk):
+    """detect_batch's walk over a batch tensor or a list of single images: chunk(x) -> list of per-image results for every chunk of at
+    most max_batch same-shape images, results in input order.  Every check runs before the first chunk."""
     if max_batch < 1:
-        raise RuntimeError('detect_batch: max_batch=%d must be positive' % max_batch)
+        raise RuntimeError('%s: max_batch=%d must be positive' % (fn, max_batch))
     if not isinstance(images, (list, tuple)):
-        x = _batch_of(images, 'images')
+        x = _batch_of(images, 'images', fn)
         if x.size(0) == 0:
-            raise RuntimeError('detect_batch: empty batch')
+            raise RuntimeError('%s: empty batch' % fn)
         out = []
         for i in range(0, x.size(0), max_batch):
-            out += _detect_chunk(net, x[i:i + max_batch], K, nms_thresh)
+            out += chunk(x[i:i + max_batch])
         return out
     if len(images) == 0:
-        raise RuntimeError('detect_batch: empty list of images')
+        raise RuntimeError('%s: empty list of images' % fn)
     one = []
     for i, im in enumerate(images):
         if torch.is_tensor(im) and im.dim() == 3:
             im = im.unsqueeze(0)
-        one.append(_batch_of(im, 'images[%d]' % i))
+        one.append(_batch_of(im, 'images[%d]' % i, fn))
         if one[-1].size(0) != 1:
-            raise RuntimeError('detect_batch: images[%d] holds %d images; a list takes single images' % (i, one[-1].size(0)))
+            raise RuntimeError('%s: images[%d] holds %d images; a list takes single images' % (fn, i, one[-1].size(0)))
     if len({im.dtype == torch.uint8 for im in one}) > 1:
-        raise RuntimeError('detect_batch: the list mixes uint8 [H,W,3] and float [3,H,W] images')
+        raise RuntimeError('%s: the list mixes uint8 [H,W,3] and float [3,H,W] images' % fn)
     groups = {}
     for i, im in enumerate(one):
         groups.setdefault((tuple(im.shape), im.dtype), []).append(i)
@@ -268,13 +280,135 @@ def detect_batch(net, images, K=10, nms_thresh=0.4, max_batch=32):
         for c in range(0, len(idx), max_batch):
             part = idx[c:c + max_batch]
             dev = next((one[i].device for i in part if one[i].is_cuda), torch.device('cuda'))
-            res = _detect_chunk(net, torch.cat([one[i].to(dev) for i in part]), K, nms_thresh)
+            res = chunk(torch.cat([one[i].to(dev) for i in part]))
             for i, r in zip(part, res):
                 out[i] = r
     return out
 
 
-def detect_plates(net, images, K=10, nms_thresh=0.4, max_batch=32, *, region):
+# ---------------------------------------------------------------------------------------------- score-threshold detection
+_THRESH_MAX_DETS = 4096          # dbx_detect_thresh_batch's bound on max_dets (one wave holds the removed set: 64 lanes x 64 bits)
+
+
+def _check_thresh(fn, score_thresh, max_dets):
+    """(float threshold, int cap) or RuntimeError: a finite real number (no bool), an integer in 1..4096 (no bool)."""
+    ok = isinstance(score_thresh, (int, float, np.integer, np.floating)) and not isinstance(score_thresh, (bool, np.bool_))
+    if not ok or not np.isfinite(float(score_thresh)):
+        raise RuntimeError('%s: score_thresh=%r must be a finite number' % (fn, score_thresh))
+    if isinstance(max_dets, (bool, np.bool_)) or not isinstance(max_dets, (int, np.integer)) or not 1 <= max_dets <= _THRESH_MAX_DETS:
+        raise RuntimeError('%s: max_dets=%r must be an integer in 1..%d' % (fn, max_dets, _THRESH_MAX_DETS))
+    return float(np.float32(score_thresh)), int(max_dets)
+
+
+def _run_thresh_batch(score_map, loc_map, score_thresh, max_dets, lm_heat=None, lm_loc=None, nms_thresh=0.4):
+    """dbx_detect_thresh_batch over [B,C,rows,cols] maps with the keep lists behind the packed rows: (arena uint8, topk int64
+    [B * max_dets], counts int32 [3 B + 1]) device tensors; _unpack_thresh reads them."""
+    B, _, rows, cols = score_map.shape
+    assert score_map.size(1) == 1 and loc_map.size() == torch.Size([B, 4, rows, cols])
+    if lm_heat is not None:
+        assert lm_heat.size() == torch.Size([B, 4, rows, cols])
+    if lm_loc is not None:
+        assert lm_loc.size() == torch.Size([B, 8, rows, cols])
+    dev = score_map.device if score_map.is_cuda else torch.device('cuda')
+
+    def f(t):
+        return None if t is None else t.detach().to(dev, torch.float32).contiguous()
+    s, l, hm, ll = f(score_map), f(loc_map), f(lm_heat), f(lm_loc)
+    dc = 5 if (hm is None and ll is None) else 13
+    arena = torch.empty(B * max_dets * dc * 8 + B * (max_dets + 1) * 4, dtype=torch.uint8, device=dev)
+    topk = torch.empty(B * max_dets, dtype=torch.int64, device=dev)
+    counts = torch.empty(3 * B + 1, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    scratch = torch.empty(L.dbx_detect_thresh_batch_scratch_bytes(B, rows, cols, max_dets), dtype=torch.uint8, device=dev)
+    check(L.dbx_detect_thresh_batch(ptr(s), ptr(l), ptr(hm), ptr(ll), B, rows, cols, float(score_thresh), max_dets, float(nms_thresh),
+                                    ptr(arena), dc, ptr(topk), ptr(arena), ptr(counts), ptr(scratch), stream_ptr()))
+    return arena, topk, counts
+
+
+def _thresh_fetch_bytes(counts, dc):
+    """bytes of the arena that hold the call's rows and keep lists, from the host copy of the counts"""
+    B = (counts.shape[0] - 1) // 3
+    return int(counts[3 * B]) * (dc * 8 + 4) + B * 4
+
+
+def _unpack_thresh(counts, arena, dc, with_totals):
+    """per image (dets [n_b, dc] float64, keep list[, pixels above the threshold]) from host arrays: the counts and the fetched arena"""
+    B = (counts.shape[0] - 1) // 3
+    prefix = counts[2 * B:]
+    total = int(prefix[B])
+    rows = arena[:total * dc * 8].view(np.float64).reshape(total, dc)
+    lists = arena[total * dc * 8:total * dc * 8 + (total + B) * 4].view(np.int32)
+    out = []
+    for b in range(B):
+        p, n = int(prefix[b]), int(counts[2 * b])
+        k = lists[p + b:p + b + n + 1]
+        r = (rows[p:p + n].copy(), [int(v) for v in k[1:1 + int(k[0])]])
+        out.append(r + (int(counts[2 * b + 1]),) if with_totals else r)
+    return out
+
+
+def _thresh_batch_eager(net, images, cap_t, nms_thresh):
+    with torch.no_grad():
+        outs = net(images)
+    s, l, hm, ll = _maps(net.KIND, outs)
+    arena, _, counts = _run_thresh_batch(s, l, cap_t[1], cap_t[0], lm_heat=hm, lm_loc=ll, nms_thresh=nms_thresh)
+    return arena, counts
+
+
+def _thresh_chunk(net, x, score_thresh, max_dets, nms_thresh, with_totals):
+    import os
+    x = (x if x.is_cuda else x.cuda()).contiguous()
+    dc = 5 if net.KIND == 'DenseBox' else 13
+    if not net.training and os.environ.get('DBX_GRAPH', '1') != '0':
+        arena, h_counts = _graph_replay(net, 'thresh', x, (max_dets, score_thresh), nms_thresh, _thresh_batch_eager, to_host='second')
+        counts = h_counts.numpy().copy()
+        nbytes = _thresh_fetch_bytes(counts, dc)
+        pin = net.__dict__.get('_thresh_pinned')
+        if pin is None or pin.numel() < nbytes:                  # grows to the largest fetch seen, never to the arena's capacity
+            pin = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8).pin_memory()
+            net.__dict__['_thresh_pinned'] = pin
+        pin[:nbytes].copy_(arena[:nbytes], non_blocking=True)    # the ONE copy whose size the counts decide, behind the replay
+        torch.cuda.current_stream().synchronize()
+        host = pin[:nbytes].numpy().copy()
+    else:
+        arena, counts = _thresh_batch_eager(net, x, (max_dets, score_thresh), nms_thresh)
+        counts = counts.cpu().numpy()
+        host = arena[:_thresh_fetch_bytes(counts, dc)].cpu().numpy()
+    return _unpack_thresh(counts, host, dc, with_totals)
+
+
+def detect_batch_thresh(net, images, score_thresh, max_dets=1024, nms_thresh=0.4, max_batch=32, with_totals=False):
+    """detect_batch with a score threshold in the place of the fixed top-K: per image EVERY pixel whose (refined) score is above
+    `score_thresh` becomes a row -- at most `max_dets` of them, the best ones when more pass -- and the reference's greedy NMS runs
+    over all of them on the device (dbx_detect_thresh_batch; the NMS handles up to 4096 rows on many CUs).  For
+    n_b = min(#{score > score_thresh}, max_dets) image b's result is bit for bit detect_batch(K = n_b)'s.
+
+    images, max_batch, chunking and list grouping: detect_batch's.  score_thresh: a finite number, compared in fp32, strictly (a score
+    equal to it is out; NaN scores never pass).  max_dets: an integer in 1..4096.
+
+    Returns, per image in input order, (dets float64 [n_b, 5|13], keep list of int); n_b may be 0 (dets.shape == (0, 5|13),
+    keep == []).  with_totals=True: 3-tuples whose last item is the number of pixels above the threshold (> n_b when the cap cut).
+
+    Eval mode replays ONE hipGraph per chunk from the cache detect() uses, under a tag of its own, keyed by (batch shape, dtype,
+    (max_dets, score_thresh), nms_thresh, compute dtype): the forward, the three decode launches and the copy of the per-image counts
+    to pinned memory; the rows and keep lists then come with ONE copy of exactly their size (one replay, two stream synchronises per
+    chunk).  Both thresholds are kernel arguments baked in at capture, as K is: SWEEPING score_thresh RE-CAPTURES at every new value,
+    and the cache holds _MAX_GRAPHS = 8 entries per network.  Train mode and DBX_GRAPH=0 run the same launches eagerly."""
+    t, cap = _check_thresh('detect_batch_thresh', score_thresh, max_dets)
+    return _detect_many('detect_batch_thresh', images, max_batch,
+                        lambda x: _thresh_chunk(net, x, t, cap, nms_thresh, bool(with_totals)))
+
+
+def _thresh_or_topk(fn, K, score_thresh, max_dets):
+    """None for the top-K path; (threshold, cap) for the threshold path, where a non-default K is a contradiction"""
+    if score_thresh is None:
+        return None
+    if K != 10:
+        raise RuntimeError('%s: K=%r and score_thresh=%r are both given; the threshold decode takes max_dets, not K' % (fn, K, score_thresh))
+    return _check_thresh(fn, score_thresh, max_dets)
+
+
+def detect_plates(net, images, K=10, nms_thresh=0.4, max_batch=32, *, region, score_thresh=None, max_dets=1024):
     """detect_batch, then perspective_transform (DenseBox.py:3446-3481, as viz_result calls it at :3546-3553) on every kept
     detection: the frames go to the device once, and ONE dbx_warp_perspective_batch_u8 launch rectifies the plates of all chunks.
 
@@ -286,25 +420,29 @@ def detect_plates(net, images, K=10, nms_thresh=0.4, max_batch=32, *, region):
     [oh, ow, 3] rectification of row keep[j], whose quad is (det[5:7], det[7:9], det[9:11], det[11:13]) = (left-up, right-up,
     right-down, left-down), or None where rectify.perspective_transform_batch gives None.  Plates are of the kind of their frame
     (CUDA tensors are views into one device arena).  detect_batch replays its cached hipGraphs in eval mode; the rectification
-    launch is NOT captured, because its size depends on the detections."""
+    launch is NOT captured, because its size depends on the detections.
+
+    score_thresh: None runs the top-K decode above; a number runs detect_batch_thresh(score_thresh, max_dets) in its place (K is then
+    ignored; a non-default K together with a threshold raises), and dets has n_b rows."""
     from . import rectify
     rectify.check_region('detect_plates', region)
+    tc = _thresh_or_topk('detect_plates', K, score_thresh, max_dets)
     if net.KIND == 'DenseBox':
         raise RuntimeError('detect_plates: DenseBox rows have no landmarks to rectify; use DenseBoxLM or DenseBoxLMLOC')
     host, kinds = rectify.host_images('detect_plates', images, 3)
     if torch.is_tensor(images):                    # one upload of the batch; the forward and the warp read the same device copy
         x = (images if images.is_cuda else images.cuda()).contiguous()
         dev = list(x.unbind(0))
-        res = detect_batch(net, x, K, nms_thresh, max_batch)
+        res = detect_batch(net, x, K, nms_thresh, max_batch) if tc is None else detect_batch_thresh(net, x, tc[0], tc[1], nms_thresh, max_batch)
     else:
         dev = rectify.to_device(images, host)
-        res = detect_batch(net, dev, K, nms_thresh, max_batch)
+        res = detect_batch(net, dev, K, nms_thresh, max_batch) if tc is None else detect_batch_thresh(net, dev, tc[0], tc[1], nms_thresh, max_batch)
     quads = [[[[d[k, 5], d[k, 6]], [d[k, 7], d[k, 8]], [d[k, 9], d[k, 10]], [d[k, 11], d[k, 12]]] for k in keep] for d, keep in res]
     plates = rectify._warp_batch(dev, kinds, quads, region)
     return [(d, keep, p) for (d, keep), p in zip(res, plates)]
 
 
-def detect_batch_resized(net, images, size=720, K=10, nms_thresh=0.4, max_batch=32):
+def detect_batch_resized(net, images, size=720, K=10, nms_thresh=0.4, max_batch=32, score_thresh=None, max_dets=1024):
     """detect_batch on frames of ANY sizes through the reference's own answer to mixed sizes: every frame is padded to a square with
     grey 128 and resized to size x size with INTER_CUBIC (pad_img + cv2.resize, batch_pad_resize, DenseBox.py:1282-1340) in ONE
     dbx_resize_cubic_batch_u8 launch, and the resulting uint8 [B, size, size, 3] tensor takes detect_batch's tensor path: a
@@ -321,13 +459,17 @@ def detect_batch_resized(net, images, size=720, K=10, nms_thresh=0.4, max_batch=
 
         res = net.detect_batch_resized(frames)
         quads = [[[d[k, 5:7], d[k, 7:9], d[k, 9:11], d[k, 11:13]] for k in keep] for d, keep in res]
-        plates = rectify.perspective_transform_batch(frames, quads, region='plate')"""
+        plates = rectify.perspective_transform_batch(frames, quads, region='plate')
+
+    score_thresh: None runs the top-K decode above; a number runs detect_batch_thresh(score_thresh, max_dets) on the resized frames
+    in its place (K is then ignored; a non-default K together with a threshold raises), and dets has n_b rows."""
     from . import rectify, resize
+    tc = _thresh_or_topk('detect_batch_resized', K, score_thresh, max_dets)
     if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or size < 4 or size % 4:
         raise RuntimeError('detect_batch_resized: size=%r must be a positive multiple of 4 (the maps are size / 4)' % (size,))
     host, _ = rectify.host_images('detect_batch_resized', images, 3)
     x = resize._pad_resize_device(rectify.to_device(images, host), int(size))
-    res = detect_batch(net, x, K, nms_thresh, max_batch)
+    res = detect_batch(net, x, K, nms_thresh, max_batch) if tc is None else detect_batch_thresh(net, x, tc[0], tc[1], nms_thresh, max_batch)
     out = []
     for im, (d, keep) in zip(host, res):
         side, pad_x, pad_y = resize.pad_geometry(im.size(0), im.size(1))

@@ -129,17 +129,24 @@ class _DenseBoxBase(nn.Module):
         from .decode import detect_batch
         return detect_batch(self, images, K, nms_thresh, max_batch)
 
-    def detect_plates(self, images, K=10, nms_thresh=0.4, max_batch=32, *, region):
+    def detect_batch_thresh(self, images, score_thresh, max_dets=1024, nms_thresh=0.4, max_batch=32, with_totals=False):
+        """detect_batch() with a score threshold in the place of the fixed top-K: every pixel above score_thresh becomes a row (at most
+        max_dets <= 4096 per image), NMS over all of them on the device; a list of (dets[n_b, 5|13], keep) in input order
+        (densebox_amd.decode.detect_batch_thresh)."""
+        from .decode import detect_batch_thresh
+        return detect_batch_thresh(self, images, score_thresh, max_dets, nms_thresh, max_batch, with_totals)
+
+    def detect_plates(self, images, K=10, nms_thresh=0.4, max_batch=32, *, region, score_thresh=None, max_dets=1024):
         """detect_batch() on uint8 frames, then every kept detection's plate rectified in one launch: a list of (dets, keep, plates)
         in input order (densebox_amd.decode.detect_plates)."""
         from .decode import detect_plates
-        return detect_plates(self, images, K, nms_thresh, max_batch, region=region)
+        return detect_plates(self, images, K, nms_thresh, max_batch, region=region, score_thresh=score_thresh, max_dets=max_dets)
 
-    def detect_batch_resized(self, images, size=720, K=10, nms_thresh=0.4, max_batch=32):
+    def detect_batch_resized(self, images, size=720, K=10, nms_thresh=0.4, max_batch=32, score_thresh=None, max_dets=1024):
         """detect_batch() on uint8 frames of any sizes, each padded to a square and resized to size x size in one launch; a list of
         (dets, keep) in input order, coordinates mapped back to the source frames (densebox_amd.decode.detect_batch_resized)."""
         from .decode import detect_batch_resized
-        return detect_batch_resized(self, images, size, K, nms_thresh, max_batch)
+        return detect_batch_resized(self, images, size, K, nms_thresh, max_batch, score_thresh, max_dets)
 
     def detect_pyramid(self, images, sizes=(480, 720, 1080), K=10, nms_thresh=0.4, max_batch=32):
         """detect_batch_resized() at every size of `sizes` with one resize launch, the rows of all levels merged in source-frame

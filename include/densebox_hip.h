@@ -50,8 +50,10 @@ const char* dbx_last_error(void);
  *   8  additions only: dbx_detect_batch, dbx_detect_batch_scratch_bytes (one decode + NMS launch over a batch of images)
  *   9  additions only: dbx_warp_job, dbx_warp_perspective_batch_u8, dbx_warp_batch_workspace_bytes (every plate of a batch in one launch)
  *  10  additions only: dbx_resize_job, dbx_resize_cubic_batch_u8, dbx_resize_batch_workspace_bytes (batched pad + bicubic resize)
- *  11  additions only: dbx_merge_xform, dbx_merge_nms_batch, dbx_merge_nms_batch_workspace_bytes (pyramid levels merged + one NMS per frame) */
-#define DBX_ABI_VERSION 11
+ *  11  additions only: dbx_merge_xform, dbx_merge_nms_batch, dbx_merge_nms_batch_workspace_bytes (pyramid levels merged + one NMS per frame)
+ *  12  additions only: dbx_detect_thresh_batch, dbx_detect_thresh_batch_scratch_bytes (score-threshold decode, packed results),
+ *      dbx_nms_large, dbx_nms_large_scratch_bytes (greedy NMS for up to 4096 rows on many CUs) */
+#define DBX_ABI_VERSION 12
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
 int dbx_device_arch(int device);
@@ -444,6 +446,42 @@ int dbx_detect_batch(const float* score, const float* loc, const float* lm_heat,
                      double* dets, int32_t det_cols, int64_t* topk_idx, int32_t* keep, void* scratch, void* stream);
 /* scratch: 5*n bytes */
 int dbx_nms(const double* dets, int32_t n, int32_t det_cols, double nms_thresh, int32_t* keep, void* scratch, void* stream);
+
+/* ---- score-threshold decode (no reference counterpart as a function; per image it IS parse_*(maps, K = n_b) + NMS, DenseBox.py:3114-3443,
+ * with n_b = min(#{score > score_thresh}, max_dets)): every pixel above the threshold becomes a row, the greedy NMS runs over all of
+ * them.  Three launches on `stream` whose grids depend on (batch, max_dets) only; no host round trip, capturable.
+ * Candidate set: score > score_thresh in fp32, strict -- a score equal to the threshold is out, NaN is never a candidate, +inf is,
+ * -0.0 > 0.0 is false; score_thresh = -inf takes every number except -inf.  When more than max_dets (1..4096) pixels pass, the max_dets
+ * best stay, in dbx_detect_batch's order: larger score first, the LOWER map index on ties (also for which of several equal scores
+ * fall under the cap) -- exactly dbx_detect_batch with K = max_dets.  Rows are written in that order by the row writer dbx_detect_batch
+ * uses; the NMS is dbx_nms's on them bit for bit (order: score descending, the HIGHER row first on ties; !(ovr <= thresh) suppresses).
+ * Maps, det_cols and the lm_heat / lm_loc conventions are dbx_detect_batch's.  Outputs (device), P = counts' prefix:
+ *   counts    int32 [batch][2] pairs (n_b, number of pixels above the threshold: > n_b when the cap cut), then int32 [batch + 1]:
+ *             P[b] = n_0 + ... + n_(b-1), P[batch] = the number of rows of the call.  3 * batch + 1 words.
+ *   dets      PACKED rows: image b's n_b rows of det_cols float64 start at row P[b].  Capacity batch * max_dets rows.
+ *   topk_idx  packed likewise: the map index of every row.  Capacity batch * max_dets.
+ *   keep      packed lists: image b's list is n_b + 1 words at word P[b] + b: the count, then the kept row numbers (0-based within the
+ *             image) in the reference's order.  Capacity batch * (max_dets + 1).  Passing keep == (int32_t*)dets asks for the lists
+ *             right BEHIND the packed rows, at byte P[batch] * det_cols * 8 of dets (capacity then batch * max_dets * det_cols * 8 +
+ *             batch * (max_dets + 1) * 4 bytes): a host reads the counts, then rows and lists with one copy of
+ *             P[batch] * (det_cols * 8 + 4) + batch * 4 bytes.
+ * Nothing else of the outputs is written (an image without candidates writes its pair, its prefix word and a zero list count).
+ * scratch: dbx_detect_thresh_batch_scratch_bytes(batch, rows, cols, max_dets) bytes (-1 for counts out of range), 256-byte-aligned
+ * base, one slice per image (a multiple of 256 bytes: rows, indices, NMS order and the max_dets x ceil(max_dets / 64)-word suppression
+ * matrix, 2 MB at 4096).  Refused with DBX_ERR_ARG before anything is launched: a null pointer (lm_heat / lm_loc excepted), batch < 1,
+ * a bad map size, max_dets outside 1..4096, a NaN score_thresh, a NaN or negative nms_thresh, det_cols other than 5 or 13 with
+ * landmark maps. */
+int64_t dbx_detect_thresh_batch_scratch_bytes(int32_t batch, int32_t rows, int32_t cols, int32_t max_dets);
+int dbx_detect_thresh_batch(const float* score, const float* loc, const float* lm_heat, const float* lm_loc,
+                            int32_t batch, int32_t rows, int32_t cols, float score_thresh, int32_t max_dets, double nms_thresh,
+                            double* dets, int32_t det_cols, int64_t* topk_idx, int32_t* keep, int32_t* counts, void* scratch,
+                            void* stream);
+/* dbx_nms (DenseBox.py:3398-3443) for 1 <= n <= 4096 rows with the same keep list on every input (ties, NaN scores and boxes included):
+ * a sort gives the order, the n x ceil(n / 64)-word suppression matrix is built by ceil(n / 64) workgroups, one wave walks it.
+ * keep [n + 1]; scratch: dbx_nms_large_scratch_bytes(n) bytes (-1 outside 1..4096).  Refused: null pointers, n outside 1..4096,
+ * det_cols < 5, a NaN or negative nms_thresh. */
+int64_t dbx_nms_large_scratch_bytes(int32_t n);
+int dbx_nms_large(const double* dets, int32_t n, int32_t det_cols, double nms_thresh, int32_t* keep, void* scratch, void* stream);
 
 /* ---- pyramid merge: the rows of `levels` runs of dbx_detect_batch over the same `batch` frames (each run on the frames resized to
  * another size) mapped back to source-frame coordinates, and ONE greedy NMS per frame over their union -- one launch, one workgroup
