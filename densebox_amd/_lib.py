@@ -157,13 +157,18 @@ SIGNATURES = {
     'dbx_nms': (C.c_int, [_VP, _I32, _I32, _D, _VP, _VP, _VP]),
     'dbx_detect_thresh_batch_scratch_bytes': (_I64, [_I32, _I32, _I32, _I32]),
     'dbx_detect_thresh_batch': (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _F, _I32, _D, _VP, _I32, _VP, _VP, _VP, _VP, _VP]),
+    'dbx_thresh_rows_batch_scratch_bytes': (_I64, [_I32, _I32, _I32, _I32]),
+    'dbx_thresh_rows_batch': (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _F, _I32, _VP, _I32, _VP, _VP, _VP, _VP]),
     'dbx_nms_large_scratch_bytes': (_I64, [_I32]),
     'dbx_nms_large': (C.c_int, [_VP, _I32, _I32, _D, _VP, _VP, _VP]),
     'dbx_merge_nms_batch_workspace_bytes': (_I64, [_I32, _I32, _I32]),
     'dbx_merge_nms_batch': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(MergeXform), _I32, _I32, _I32, _I32, _D, _VP, _VP, _VP, _VP]),
+    'dbx_merge_nms_thresh_batch_workspace_bytes': (_I64, [_I32, _I32, _I32]),
+    'dbx_merge_nms_thresh_batch': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(MergeXform), _I32, _I32, _I32, _I32, _D,
+                                             _VP, _VP, _VP, _VP, _VP]),
 }
 
-ABI_VERSION = 12         # include/densebox_hip.h DBX_ABI_VERSION this binding was written against
+ABI_VERSION = 13         # include/densebox_hip.h DBX_ABI_VERSION this binding was written against
 _lib = None
 MISSING = []
 

@@ -616,6 +616,13 @@ static int64_t merge_slice_bytes(int64_t n) {
 }
 static_assert(sizeof(dbx_merge_xform) == 24, "dbx_merge_xform layout");
 
+// one column of a level row in source-frame coordinates: x columns 0, 2, 5, 7, 9, 11, y columns 1, 3, 6, 8, 10, 12, the score copied
+__device__ __forceinline__ double merge_map_col(double v, int col, const dbx_merge_xform& t) {
+    if (col == 4) return v;
+    const bool is_x = col < 4 ? !(col & 1) : (col & 1);
+    return v * t.scale - (is_x ? t.off_x : t.off_y);
+}
+
 __global__ __launch_bounds__(DET_THREADS) void merge_nms_kernel(const double* const* __restrict__ level_dets,
                                                                 const dbx_merge_xform* __restrict__ xform, int levels, int batch, int K,
                                                                 int dc, double thresh, double* __restrict__ out_dets, int* out_keep,
@@ -627,13 +634,7 @@ __global__ __launch_bounds__(DET_THREADS) void merge_nms_kernel(const double* co
     for (long long e = threadIdx.x; e < ne; e += blockDim.x) {
         const int row = (int)(e / dc), col = (int)(e - (long long)row * dc);
         const int l = row / K, r = row - l * K;
-        double v = level_dets[l][(b * (size_t)K + (size_t)r) * (size_t)dc + (size_t)col];
-        if (col != 4) {
-            const dbx_merge_xform t = xform[(size_t)l * batch + b];
-            const bool is_x = col < 4 ? !(col & 1) : (col & 1);   // x: 0, 2, 5, 7, 9, 11; y: 1, 3, 6, 8, 10, 12
-            v = v * t.scale - (is_x ? t.off_x : t.off_y);
-        }
-        o[e] = v;
+        o[e] = merge_map_col(level_dets[l][(b * (size_t)K + (size_t)r) * (size_t)dc + (size_t)col], col, xform[(size_t)l * batch + b]);
     }
     __threadfence_block();
     __syncthreads();
@@ -732,18 +733,17 @@ __device__ __forceinline__ void bitonic_desc_u64(unsigned long long* a, int P2) 
         }
 }
 
-__global__ __launch_bounds__(DET_THREADS) void thresh_select_kernel(const ThrArgs a) {
+// The select stage of image b = blockIdx.x, shared by dbx_detect_thresh_batch and dbx_thresh_rows_batch: threshold + compaction, the
+// radix select past the cap, the sort, the rows (rows_fs [cap][dc]) and map indices (topk_fs [cap]) of the image and its count pair.
+// ORDER: also the NMS order of the rows (order [cap]); without it `order` is not touched.
+template <bool ORDER>
+__device__ __forceinline__ void thresh_select_image(const ThrArgs& a, double* rows_fs, long long* topk_fs, int* order) {
     const size_t b = blockIdx.x;
     const int tid = threadIdx.x, n = a.rows * a.cols, cap = a.cap;
     const float* score = a.score + b * (size_t)n;
     const float* loc = a.loc + b * 4 * (size_t)n;
     const float* lm_heat = a.lm_heat ? a.lm_heat + b * 4 * (size_t)n : nullptr;
     const float* lm_loc = a.lm_loc ? a.lm_loc + b * 8 * (size_t)n : nullptr;
-    const ThrLayout L = thr_layout(cap);
-    unsigned char* const s = a.scratch + b * (size_t)L.total;
-    double* const rows_fs = (double*)s;
-    long long* const topk_fs = (long long*)(s + L.topk);
-    int* const order = (int*)(s + L.order);
     __shared__ float red_v[DET_THREADS / 64];
     __shared__ int red_i[DET_THREADS / 64];
     __shared__ int lm_arg[4];
@@ -785,14 +785,28 @@ __global__ __launch_bounds__(DET_THREADS) void thresh_select_kernel(const ThrArg
         const int idx = (int)(~(unsigned)(c & 0xffffffffull));
         det_write_row(rows_fs + (size_t)r * a.dc, idx, score, loc, lm_loc, lm_arg, n, a.cols, a.dc);
         topk_fs[r] = idx;
-        int lo = 0, hi = r;                                         // first position whose key is <= key
-        while (lo < hi) { const int m = (lo + hi) >> 1; if ((unsigned)(cand[m] >> 32) > key) lo = m + 1; else hi = m; }
-        const int rs = lo;
-        lo = r + 1; hi = nb;                                        // first position whose key is < key
-        while (lo < hi) { const int m = (lo + hi) >> 1; if ((unsigned)(cand[m] >> 32) >= key) lo = m + 1; else hi = m; }
-        order[rs + (lo - 1 - r)] = r;
+        if (ORDER) {
+            int lo = 0, hi = r;                                     // first position whose key is <= key
+            while (lo < hi) { const int m = (lo + hi) >> 1; if ((unsigned)(cand[m] >> 32) > key) lo = m + 1; else hi = m; }
+            const int rs = lo;
+            lo = r + 1; hi = nb;                                    // first position whose key is < key
+            while (lo < hi) { const int m = (lo + hi) >> 1; if ((unsigned)(cand[m] >> 32) >= key) lo = m + 1; else hi = m; }
+            order[rs + (lo - 1 - r)] = r;
+        }
     }
     if (tid == 0) { a.counts[2 * b] = nb; a.counts[2 * b + 1] = (int)total; }
+}
+
+__global__ __launch_bounds__(DET_THREADS) void thresh_select_kernel(const ThrArgs a) {
+    const ThrLayout L = thr_layout(a.cap);
+    unsigned char* const s = a.scratch + blockIdx.x * (size_t)L.total;
+    thresh_select_image<true>(a, (double*)s, (long long*)(s + L.topk), (int*)(s + L.order));
+}
+
+// dbx_thresh_rows_batch: the select stage alone, straight into the caller's [batch][cap] slots (a.dets, a.topk)
+__global__ __launch_bounds__(DET_THREADS) void thresh_rows_kernel(const ThrArgs a) {
+    const size_t r0 = blockIdx.x * (size_t)a.cap;
+    thresh_select_image<false>(a, a.dets + r0 * a.dc, a.topk + r0, nullptr);
 }
 
 // Rows [64 rb, 64 rb + 64) (in NMS order: position p is row order[p] of dets) of the n x nw suppression matrix, the words at or right of
@@ -941,25 +955,47 @@ extern "C" int dbx_detect_thresh_batch(const float* score, const float* loc, con
     return DBX_OK;
 }
 
+// ---- dbx_thresh_rows_batch: launch 1 alone, for a caller that merges the rows of several runs before the NMS (the threshold pyramid).
+// The kernel works in LDS and writes straight into the caller's slots; the scratch argument is kept in the contract (a non-null
+// pointer of dbx_thresh_rows_batch_scratch_bytes) so that a later version may stage through global memory without an ABI change.
+extern "C" int64_t dbx_thresh_rows_batch_scratch_bytes(int32_t batch, int32_t rows, int32_t cols, int32_t max_dets) {
+    if (batch < 1 || rows < 1 || cols < 1 || max_dets < 1 || max_dets > THR_MAX_DETS) return -1;
+    return 256;
+}
+
+extern "C" int dbx_thresh_rows_batch(const float* score, const float* loc, const float* lm_heat, const float* lm_loc, int32_t batch,
+                                     int32_t rows, int32_t cols, float score_thresh, int32_t max_dets, double* dets, int32_t det_cols,
+                                     int64_t* topk_idx, int32_t* counts, void* scratch, void* stream) {
+    DBX_REQUIRE(score && loc && dets && topk_idx && counts && scratch, "thresh_rows_batch: null argument");
+    DBX_REQUIRE(batch > 0, "thresh_rows_batch: batch=%d must be positive", batch);
+    DBX_REQUIRE(rows > 0 && cols > 0 && (int64_t)rows * cols <= 0x7fffffff, "thresh_rows_batch: bad map size %d x %d", rows, cols);
+    DBX_REQUIRE(max_dets >= 1 && max_dets <= THR_MAX_DETS, "thresh_rows_batch: max_dets=%d must be 1..%d", max_dets, THR_MAX_DETS);
+    DBX_REQUIRE(!std::isnan(score_thresh), "thresh_rows_batch: score_thresh is NaN");
+    DBX_REQUIRE(det_cols == 5 || (det_cols == 13 && (lm_heat || lm_loc)), "thresh_rows_batch: det_cols must be 5, or 13 with landmark maps");
+    DBX_REQUIRE((int64_t)batch * max_dets <= 0x7fffffff / 16, "thresh_rows_batch: batch * max_dets = %lld rows do not fit an int32 row number",
+                (long long)batch * max_dets);
+    ThrArgs a;
+    a.score = score; a.loc = loc; a.lm_heat = lm_heat; a.lm_loc = lm_loc;
+    a.batch = batch; a.rows = rows; a.cols = cols; a.dc = det_cols; a.cap = max_dets;
+    a.keep_behind_rows = 0;
+    a.t = score_thresh; a.thresh = 0.0;
+    a.dets = dets; a.topk = (long long*)topk_idx; a.keep = nullptr; a.counts = counts; a.scratch = (unsigned char*)scratch;
+    hipLaunchKernelGGL(thresh_rows_kernel, dim3(batch), dim3(DET_THREADS), 0, (hipStream_t)stream, a);
+    DBX_LAUNCH_CHECK();
+    return DBX_OK;
+}
+
 // ---- dbx_nms_large: the same matrix + sweep on caller rows.  The order comes from a bitonic sort of (score key, row) pairs in LDS
 // (48 KB): key = the float64 score's bits made order-preserving, -0 == +0, every NaN the largest; larger key first, the higher row first
 // among equal keys -- nms_block's rank for every input.
-__global__ __launch_bounds__(DET_THREADS) void nms_large_order_kernel(const double* dets, int n, int dc, int* order) {
-    __shared__ unsigned long long key[THR_MAX_DETS];
-    __shared__ int row[THR_MAX_DETS];
-    int P2 = 2;
-    while (P2 < n) P2 <<= 1;
-    for (int i = threadIdx.x; i < P2; i += DET_THREADS) {
-        unsigned long long k = 0ull;                                 // padding: below -inf's key
-        if (i < n) {
-            const double sc = dets[(size_t)i * dc + 4];
-            if (sc != sc) k = ~0ull;
-            else if (sc == 0.0) k = 0x8000000000000000ull;
-            else { const unsigned long long u = (unsigned long long)__double_as_longlong(sc); k = (u >> 63) ? ~u : (u | 0x8000000000000000ull); }
-        }
-        key[i] = k; row[i] = i < n ? i : -1;
-    }
-    __syncthreads();
+__device__ __forceinline__ unsigned long long nmsl_score_key(double sc) {
+    if (sc != sc) return ~0ull;
+    if (sc == 0.0) return 0x8000000000000000ull;
+    const unsigned long long u = (unsigned long long)__double_as_longlong(sc);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+// bitonic sort of the (key, row) pairs [0, P2) in LDS by a DET_THREADS-wide workgroup into that order (a barrier in front is the caller's)
+__device__ __forceinline__ void nmsl_sort_pairs(unsigned long long* key, int* row, int P2) {
     for (int size = 2; size <= P2; size <<= 1)
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
             for (int t = threadIdx.x; t < (P2 >> 1); t += DET_THREADS) {
@@ -971,6 +1007,18 @@ __global__ __launch_bounds__(DET_THREADS) void nms_large_order_kernel(const doub
             }
             __syncthreads();
         }
+}
+__global__ __launch_bounds__(DET_THREADS) void nms_large_order_kernel(const double* dets, int n, int dc, int* order) {
+    __shared__ unsigned long long key[THR_MAX_DETS];
+    __shared__ int row[THR_MAX_DETS];
+    int P2 = 2;
+    while (P2 < n) P2 <<= 1;
+    for (int i = threadIdx.x; i < P2; i += DET_THREADS) {
+        key[i] = i < n ? nmsl_score_key(dets[(size_t)i * dc + 4]) : 0ull;      // padding: below -inf's key
+        row[i] = i < n ? i : -1;
+    }
+    __syncthreads();
+    nmsl_sort_pairs(key, row, P2);
     for (int i = threadIdx.x; i < n; i += DET_THREADS) order[i] = row[i];
 }
 __global__ __launch_bounds__(NMSL_THREADS) void nms_large_mask_kernel(const double* dets, int n, int dc, double thresh, const int* order,
@@ -1001,6 +1049,153 @@ extern "C" int dbx_nms_large(const double* dets, int32_t n, int32_t det_cols, do
     DBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(nms_large_sweep_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const unsigned long long*)mask, (const int*)order, n,
                        keep);
+    DBX_LAUNCH_CHECK();
+    return DBX_OK;
+}
+
+// ---- dbx_merge_nms_thresh_batch: dbx_merge_nms_batch over the variable row counts dbx_thresh_rows_batch leaves on the device.  Three
+// launches whose grids depend on (levels, batch, max_dets) alone; the counts are read on the device and clamped to 0..max_dets there.
+//   1. merge_thresh_pack_kernel, one workgroup per frame: its level counts and the unions of the frames before it give P[b]; the rows
+//      go, mapped by merge_map_col, to rows P[b].. of out_dets level by level; the thread that copies a score also files the
+//      (nmsl_score_key, union row) pair in LDS, and nmsl_sort_pairs gives the NMS order (dbx_nms_large's, 48 KB).
+//   2. merge_thresh_mask_kernel, grid (ceil(levels * max_dets / 64), batch): nmsl_mask_rows on the frame's packed rows; workgroups
+//      past m_b leave at once.
+//   3. merge_thresh_sweep_kernel, one wave per frame: nmsl_sweep into the frame's packed keep list.
+// workspace: [levels row pointers][levels count pointers][levels * batch transforms] to 256 B, then per frame
+// order [levels * max_dets] int32 (to 256 B) | matrix [levels * max_dets][ceil(levels * max_dets / 64)] words
+struct MergeThrArgs {
+    const double* const* level_dets; const int* const* level_counts; const dbx_merge_xform* xform;
+    int levels, batch, cap, dc, keep_behind_rows;
+    double thresh;
+    double* out_dets; int* out_keep; int* out_counts;
+    unsigned char* slices;
+};
+struct MergeThrLayout { long long mask, total; int nw; };
+static __host__ __device__ inline MergeThrLayout merge_thr_layout(int nmax) {
+    MergeThrLayout L;
+    L.nw = (nmax + 63) / 64;
+    L.mask = thr_up256((long long)nmax * 4);
+    L.total = L.mask + thr_up256((long long)nmax * L.nw * 8);
+    return L;
+}
+static int64_t merge_thr_head_bytes(int32_t levels, int32_t batch) {
+    return thr_up256((int64_t)levels * 16 + (int64_t)levels * batch * (int64_t)sizeof(dbx_merge_xform));
+}
+__device__ __forceinline__ int merge_thr_count(const MergeThrArgs& a, int l, int b) {      // n_(l,b), never trusted as it stands
+    return min(max(a.level_counts[l][2 * b], 0), a.cap);
+}
+
+__global__ __launch_bounds__(DET_THREADS) void merge_thresh_pack_kernel(const MergeThrArgs a) {
+    __shared__ unsigned long long key[THR_MAX_DETS];
+    __shared__ int row[THR_MAX_DETS];
+    __shared__ int s_pre, s_mine, s_tot;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) { s_pre = 0; s_mine = 0; s_tot = 0; }
+    __syncthreads();
+    int pre = 0, mine = 0, tot = 0;
+    for (int i = tid; i < a.levels * a.batch; i += DET_THREADS) {
+        const int l = i / a.batch, j = i - l * a.batch, c = merge_thr_count(a, l, j);
+        tot += c; pre += j < b ? c : 0; mine += j == b ? c : 0;
+    }
+    atomicAdd(&s_pre, pre); atomicAdd(&s_mine, mine); atomicAdd(&s_tot, tot);
+    __syncthreads();
+    pre = s_pre; tot = s_tot;
+    const int m = s_mine;                                            // <= levels * cap <= MERGE_MAX_ROWS
+    int* const pairs = a.out_counts + (size_t)b * a.levels * 2;
+    for (int l = tid; l < a.levels; l += DET_THREADS) { pairs[2 * l] = merge_thr_count(a, l, b); pairs[2 * l + 1] = a.level_counts[l][2 * b + 1]; }
+    int* const prefix = a.out_counts + (size_t)a.batch * a.levels * 2;
+    if (tid == 0) { prefix[b] = pre; if (b == a.batch - 1) prefix[a.batch] = tot; }
+    if (m == 0) return;
+    double* const o = a.out_dets + (size_t)pre * a.dc;
+    int u0 = 0;                                                      // union row of the level's row 0
+    for (int l = 0; l < a.levels; ++l) {
+        const int nl = merge_thr_count(a, l, b);                     // (uniform)
+        const double* src = a.level_dets[l] + (size_t)b * a.cap * a.dc;
+        const dbx_merge_xform t = a.xform[(size_t)l * a.batch + b];
+        for (int e = tid; e < nl * a.dc; e += DET_THREADS) {
+            const int r = e / a.dc, col = e - r * a.dc;
+            const double v = src[e];
+            o[(size_t)u0 * a.dc + e] = merge_map_col(v, col, t);
+            if (col == 4) { key[u0 + r] = nmsl_score_key(v); row[u0 + r] = u0 + r; }
+        }
+        u0 += nl;
+    }
+    int P2 = 2;
+    while (P2 < m) P2 <<= 1;
+    for (int i = m + tid; i < P2; i += DET_THREADS) { key[i] = 0ull; row[i] = -1; }      // padding: below -inf's key
+    __syncthreads();
+    nmsl_sort_pairs(key, row, P2);
+    int* const order = (int*)(a.slices + (size_t)b * merge_thr_layout(a.levels * a.cap).total);
+    for (int i = tid; i < m; i += DET_THREADS) order[i] = row[i];
+}
+
+__global__ __launch_bounds__(NMSL_THREADS) void merge_thresh_mask_kernel(const MergeThrArgs a) {
+    const int rb = blockIdx.x, b = blockIdx.y;
+    const int* const prefix = a.out_counts + (size_t)a.batch * a.levels * 2;
+    const int pre = prefix[b], m = min(prefix[b + 1] - pre, a.levels * a.cap);
+    if (64 * rb >= m) return;
+    const MergeThrLayout L = merge_thr_layout(a.levels * a.cap);
+    unsigned char* const s = a.slices + (size_t)b * L.total;
+    nmsl_mask_rows(a.out_dets + (size_t)pre * a.dc, a.dc, (const int*)s, m, a.thresh, (unsigned long long*)(s + L.mask), L.nw, rb);
+}
+
+__global__ __launch_bounds__(64) void merge_thresh_sweep_kernel(const MergeThrArgs a) {
+    const int b = blockIdx.x;
+    const int* const prefix = a.out_counts + (size_t)a.batch * a.levels * 2;
+    const int pre = prefix[b], m = min(prefix[b + 1] - pre, a.levels * a.cap), tot = prefix[a.batch];
+    int* const keep = (a.keep_behind_rows ? (int*)(a.out_dets + (size_t)tot * a.dc) : a.out_keep) + (size_t)pre + b;
+    const MergeThrLayout L = merge_thr_layout(a.levels * a.cap);
+    const unsigned char* s = a.slices + (size_t)b * L.total;
+    nmsl_sweep((const unsigned long long*)(s + L.mask), L.nw, (const int*)s, m, keep);
+}
+
+extern "C" int64_t dbx_merge_nms_thresh_batch_workspace_bytes(int32_t levels, int32_t batch, int32_t max_dets) {
+    if (levels < 1 || batch < 1 || max_dets < 1 || max_dets > THR_MAX_DETS || (int64_t)levels * max_dets > MERGE_MAX_ROWS) return -1;
+    return merge_thr_head_bytes(levels, batch) + (int64_t)batch * merge_thr_layout(levels * max_dets).total;
+}
+
+extern "C" int dbx_merge_nms_thresh_batch(const double* const* level_dets, const int32_t* const* level_counts, const dbx_merge_xform* xform,
+                                          int32_t levels, int32_t batch, int32_t max_dets, int32_t det_cols, double nms_thresh,
+                                          double* out_dets, int32_t* out_keep, int32_t* out_counts, void* workspace, void* stream) {
+    DBX_REQUIRE(levels >= 1, "merge_nms_thresh_batch: levels=%d must be positive", levels);
+    DBX_REQUIRE(batch >= 1, "merge_nms_thresh_batch: batch=%d must be positive", batch);
+    DBX_REQUIRE(max_dets >= 1 && max_dets <= THR_MAX_DETS, "merge_nms_thresh_batch: max_dets=%d must be 1..%d", max_dets, THR_MAX_DETS);
+    DBX_REQUIRE(det_cols == 5 || det_cols == 13, "merge_nms_thresh_batch: det_cols=%d must be 5 or 13", det_cols);
+    DBX_REQUIRE((int64_t)levels * max_dets <= MERGE_MAX_ROWS, "merge_nms_thresh_batch: levels * max_dets = %lld rows per frame exceed %d",
+                (long long)levels * max_dets, MERGE_MAX_ROWS);
+    DBX_REQUIRE(!std::isnan(nms_thresh) && nms_thresh >= 0.0, "merge_nms_thresh_batch: nms_thresh=%g must be a number >= 0", nms_thresh);
+    DBX_REQUIRE(level_dets && level_counts && xform && out_dets && out_keep && out_counts && workspace, "merge_nms_thresh_batch: null argument");
+    DBX_REQUIRE((int64_t)batch * levels * max_dets <= 0x7fffffff / 16, "merge_nms_thresh_batch: batch * levels * max_dets = %lld rows do not fit the packed arena's int32 prefix",
+                (long long)batch * levels * max_dets);
+    for (int l = 0; l < levels; ++l)
+        DBX_REQUIRE(level_dets[l] && level_counts[l], "merge_nms_thresh_batch: level %d has a null row or count pointer", l);
+    for (int64_t i = 0; i < (int64_t)levels * batch; ++i) {
+        const dbx_merge_xform& t = xform[i];
+        DBX_REQUIRE(std::isfinite(t.scale) && t.scale > 0.0, "merge_nms_thresh_batch: level %d frame %d has scale %g (finite and positive needed)",
+                    (int)(i / batch), (int)(i % batch), t.scale);
+        DBX_REQUIRE(std::isfinite(t.off_x) && std::isfinite(t.off_y), "merge_nms_thresh_batch: level %d frame %d has a non-finite offset",
+                    (int)(i / batch), (int)(i % batch));
+    }
+    // device records, as in dbx_merge_nms_batch (pageable source: the copy has read the vector when it returns)
+    const int64_t head = merge_thr_head_bytes(levels, batch);
+    std::vector<unsigned char> rec((size_t)head, 0);
+    memcpy(rec.data(), level_dets, (size_t)levels * 8);
+    memcpy(rec.data() + (size_t)levels * 8, level_counts, (size_t)levels * 8);
+    memcpy(rec.data() + (size_t)levels * 16, xform, (size_t)levels * batch * sizeof(dbx_merge_xform));
+    unsigned char* ws = (unsigned char*)workspace;
+    DBX_HIP(hipMemcpyAsync(ws, rec.data(), (size_t)head, hipMemcpyHostToDevice, (hipStream_t)stream));
+    MergeThrArgs a;
+    a.level_dets = (const double* const*)ws; a.level_counts = (const int* const*)(ws + (size_t)levels * 8);
+    a.xform = (const dbx_merge_xform*)(ws + (size_t)levels * 16);
+    a.levels = levels; a.batch = batch; a.cap = max_dets; a.dc = det_cols;
+    a.keep_behind_rows = (const void*)out_keep == (const void*)out_dets;
+    a.thresh = nms_thresh;
+    a.out_dets = out_dets; a.out_keep = out_keep; a.out_counts = out_counts; a.slices = ws + head;
+    hipLaunchKernelGGL(merge_thresh_pack_kernel, dim3(batch), dim3(DET_THREADS), 0, (hipStream_t)stream, a);
+    DBX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(merge_thresh_mask_kernel, dim3((levels * max_dets + 63) / 64, batch), dim3(NMSL_THREADS), 0, (hipStream_t)stream, a);
+    DBX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(merge_thresh_sweep_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, a);
     DBX_LAUNCH_CHECK();
     return DBX_OK;
 }

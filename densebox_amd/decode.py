@@ -121,7 +121,7 @@ def _graph_replay(net, tag, image, K, nms_thresh, eager, to_host=True):
     detect(), detect_batch() and detect_pyramid(): keyed by (tag, input shape, input dtype, K, threshold, compute dtype),
     re-captured when the weight signature changes, at most _MAX_GRAPHS entries (LRU).
 
-    to_host=False (detect_pyramid's 'level' entries): nothing is copied and nothing waits -- the replay is queued and the entry's
+    to_host=False (detect_pyramid's 'level' and 'level_thresh' entries): nothing is copied and nothing waits -- the replay is queued and the entry's
     own device (dets, keep) are returned, valid in stream order until the entry's next replay.
 
     to_host='second' (detect_batch_thresh's entries, K = (max_dets, score_thresh)): only the second result, the counts, is copied
@@ -513,7 +513,127 @@ def _merge_nms(level_dets, xform, nms_thresh, out_dets, out_keep):
     check(L.dbx_merge_nms_batch(ptrs, xf, levels, b, K, dc, float(nms_thresh), ptr(out_dets), ptr(out_keep), ptr(ws), stream_ptr()))
 
 
-def detect_pyramid(net, images, sizes=(480, 720, 1080), K=10, nms_thresh=0.4, max_batch=32):
+def _run_thresh_rows(score_map, loc_map, score_thresh, max_dets, lm_heat=None, lm_loc=None):
+    """dbx_thresh_rows_batch over [B,C,rows,cols] maps: (dets float64 [B, max_dets, 5|13], topk int64 [B, max_dets], counts int32 [B, 2])
+    device tensors in slot layout; only the first counts[b, 0] rows of image b are written."""
+    B, _, rows, cols = score_map.shape
+    assert score_map.size(1) == 1 and loc_map.size() == torch.Size([B, 4, rows, cols])
+    if lm_heat is not None:
+        assert lm_heat.size() == torch.Size([B, 4, rows, cols])
+    if lm_loc is not None:
+        assert lm_loc.size() == torch.Size([B, 8, rows, cols])
+    dev = score_map.device if score_map.is_cuda else torch.device('cuda')
+
+    def f(t):
+        return None if t is None else t.detach().to(dev, torch.float32).contiguous()
+    s, l, hm, ll = f(score_map), f(loc_map), f(lm_heat), f(lm_loc)
+    dc = 5 if (hm is None and ll is None) else 13
+    dets = torch.empty((B, max_dets, dc), dtype=torch.float64, device=dev)
+    topk = torch.empty((B, max_dets), dtype=torch.int64, device=dev)
+    counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    scratch = torch.empty(L.dbx_thresh_rows_batch_scratch_bytes(B, rows, cols, max_dets), dtype=torch.uint8, device=dev)
+    check(L.dbx_thresh_rows_batch(ptr(s), ptr(l), ptr(hm), ptr(ll), B, rows, cols, float(score_thresh), max_dets, ptr(dets), dc,
+                                  ptr(topk), ptr(counts), ptr(scratch), stream_ptr()))
+    return dets, topk, counts
+
+
+def _thresh_rows_eager(net, images, cap_t, nms_thresh):
+    with torch.no_grad():
+        outs = net(images)
+    s, l, hm, ll = _maps(net.KIND, outs)
+    dets, _, counts = _run_thresh_rows(s, l, cap_t[1], cap_t[0], lm_heat=hm, lm_loc=ll)
+    return dets, counts
+
+
+def _merge_nms_thresh(level_dets, level_counts, xform, nms_thresh, arena, out_counts):
+    """ONE dbx_merge_nms_thresh_batch call: level_dets / level_counts lists of L device [b, max_dets, dc] float64 / [b, 2] int32 tensors
+    (_run_thresh_rows), xform [L][b] triples; arena uint8 (packed rows, the keep lists right behind them), out_counts int32
+    [2 * b * L + b + 1], both on the device."""
+    levels, (b, cap, dc) = len(level_dets), level_dets[0].shape
+    dp = (C.c_void_p * levels)(*[t.data_ptr() for t in level_dets])
+    cp = (C.c_void_p * levels)(*[t.data_ptr() for t in level_counts])
+    xf = (_lib.MergeXform * (levels * b))()
+    for l in range(levels):
+        for i in range(b):
+            xf[l * b + i].scale, xf[l * b + i].off_x, xf[l * b + i].off_y = xform[l][i]
+    L = _lib.lib()
+    ws = torch.empty(L.dbx_merge_nms_thresh_batch_workspace_bytes(levels, b, cap), dtype=torch.uint8, device=arena.device)
+    check(L.dbx_merge_nms_thresh_batch(dp, cp, xf, levels, b, cap, dc, float(nms_thresh), ptr(arena), ptr(arena), ptr(out_counts), ptr(ws),
+                                       stream_ptr()))
+
+
+def _pyramid_counts_words(b, levels):
+    return 2 * b * levels + b + 1
+
+
+def _pyramid_thresh_fetch_bytes(counts, levels, dc):
+    """bytes of a chunk's arena that hold its rows and keep lists, from the host copy of the chunk's merge counts
+    ([b][levels][2] pairs, then the [b + 1] prefix of the union sizes)"""
+    b = (counts.shape[0] - 1) // (2 * levels + 1)
+    return int(counts[-1]) * (dc * 8 + 4) + b * 4
+
+
+def _unpack_pyramid_thresh(counts, arena, levels, dc, with_levels):
+    """per frame (dets [m_b, dc] float64, keep list[, rows per level]) from host arrays: a chunk's merge counts and its fetched arena"""
+    b = (counts.shape[0] - 1) // (2 * levels + 1)
+    pairs, prefix = counts[:2 * b * levels].reshape(b, levels, 2), counts[2 * b * levels:]
+    total = int(prefix[b])
+    rows = arena[:total * dc * 8].view(np.float64).reshape(total, dc)
+    lists = arena[total * dc * 8:total * dc * 8 + (total + b) * 4].view(np.int32)
+    out = []
+    for i in range(b):
+        p, m = int(prefix[i]), int(prefix[i + 1] - prefix[i])
+        k = lists[p + i:p + i + m + 1]
+        r = (rows[p:p + m].copy(), [int(v) for v in k[1:1 + int(k[0])]])
+        out.append(r + (pairs[i, :, 0].astype(np.int64),) if with_levels else r)
+    return out
+
+
+def _pyramid_thresh(net, levels, xform, B, t, cap, nms_thresh, max_batch, graph, with_levels):
+    """detect_pyramid's threshold path over the resized levels: everything is queued first, then the counts come to the host, then
+    exactly the rows and lists"""
+    nl = len(levels)
+    dc = 5 if net.KIND == 'DenseBox' else 13
+    dev = levels[0].device
+    spans = [(c0, min(B, c0 + max_batch)) for c0 in range(0, B, max_batch)]
+    offs = np.cumsum([0] + [_pyramid_counts_words(c1 - c0, nl) for c0, c1 in spans])
+    counts_dev = torch.empty(int(offs[-1]), dtype=torch.int32, device=dev)
+    arenas = []
+    for (c0, c1), o0, o1 in zip(spans, offs[:-1], offs[1:]):
+        rows, cnts = [], []
+        for lv in levels:
+            x = lv[c0:c1]
+            if graph:        # the entry's device rows and counts: overwritten by its next replay, queued behind this chunk's merge
+                d, c = _graph_replay(net, 'level_thresh', x, (cap, t), nms_thresh, _thresh_rows_eager, to_host=False)
+            else:
+                d, c = _thresh_rows_eager(net, x, (cap, t), nms_thresh)
+            rows.append(d)
+            cnts.append(c)
+        b = c1 - c0
+        arena = torch.empty(b * nl * cap * (dc * 8 + 4) + b * 4, dtype=torch.uint8, device=dev)
+        _merge_nms_thresh(rows, cnts, [xf[c0:c1] for xf in xform], nms_thresh, arena, counts_dev[int(o0):int(o1)])
+        arenas.append(arena)
+    counts = counts_dev.cpu().numpy()                                # the first wait of the call
+    parts = [counts[int(o0):int(o1)] for o0, o1 in zip(offs[:-1], offs[1:])]
+    nbytes = [_pyramid_thresh_fetch_bytes(c, nl, dc) for c in parts]
+    pin = net.__dict__.get('_thresh_pinned')
+    if pin is None or pin.numel() < sum(nbytes):                     # grows to the largest fetch seen, never to the arenas' capacity
+        pin = torch.empty(max(sum(nbytes), 1 << 16), dtype=torch.uint8).pin_memory()
+        net.__dict__['_thresh_pinned'] = pin
+    at = np.cumsum([0] + nbytes)
+    for arena, a0, nb in zip(arenas, at[:-1], nbytes):
+        pin[int(a0):int(a0) + nb].copy_(arena[:nb], non_blocking=True)
+    torch.cuda.current_stream().synchronize()                        # the second and last
+    host = pin[:int(at[-1])].numpy().copy()
+    out = []
+    for c, a0, nb in zip(parts, at[:-1], nbytes):
+        out += _unpack_pyramid_thresh(c, host[int(a0):int(a0) + nb], nl, dc, with_levels)
+    return out
+
+
+def detect_pyramid(net, images, sizes=(480, 720, 1080), K=10, nms_thresh=0.4, max_batch=32, score_thresh=None, max_dets=1024,
+                   with_levels=False):
     """Multi-scale detection, the test-time image pyramid of the DenseBox paper: every frame is padded to a square and resized to
     EVERY size of `sizes` (what detect_batch_resized does for one size) in ONE dbx_resize_cubic_batch_u8 launch; per chunk of at most
     `max_batch` frames each level runs one forward + one dbx_detect_batch (in eval mode a cached hipGraph per level shape whose rows
@@ -534,10 +654,25 @@ def detect_pyramid(net, images, sizes=(480, 720, 1080), K=10, nms_thresh=0.4, ma
 
         res = net.detect_pyramid(frames)
         quads = [[[d[k, 5:7], d[k, 7:9], d[k, 9:11], d[k, 11:13]] for k in keep] for d, keep in res]
-        plates = rectify.perspective_transform_batch(frames, quads, region='plate')"""
+        plates = rectify.perspective_transform_batch(frames, quads, region='plate')
+
+    score_thresh: None runs the top-K decode above.  A number (max_dets an integer with len(sizes) * max_dets <= 4096; K is then ignored,
+    and a non-default K together with a threshold raises) makes every level decode every pixel above the threshold, as
+    detect_batch_thresh does: per chunk and level one forward + one dbx_thresh_rows_batch (a cached hipGraph per level shape under a
+    tag of its own, keyed by (max_dets, score_thresh); rows and counts stay on the device), then ONE dbx_merge_nms_thresh_batch per
+    chunk reads the counts on the device, packs the mapped rows of each frame and runs the NMS over its union of m_b rows.  The host
+    waits twice per call: for the counts of all chunks, then for exactly the rows and lists they announce.  Returns, per frame in input
+    order, (dets float64 [m_b, 5|13], keep); m_b may be 0.  with_levels=True adds a third item, the int array [len(sizes)] of the rows
+    each level gave (the level of row i follows from its cumulative sum).  The result is bit for bit detect_batch_resized(frames,
+    size=s, score_thresh=..., max_dets=..., max_batch=...) per size, the rows of each frame concatenated in the order of `sizes`, and
+    decode.NMS over them."""
     import os
     from . import rectify, resize
     sizes = _check_pyramid_sizes(sizes)
+    tc = _thresh_or_topk('detect_pyramid', K, score_thresh, max_dets)
+    if tc is not None and len(sizes) * tc[1] > _MERGE_MAX_ROWS:
+        raise RuntimeError('detect_pyramid: len(sizes)=%d levels x max_dets=%d rows exceed %d rows per frame'
+                           % (len(sizes), tc[1], _MERGE_MAX_ROWS))
     if isinstance(max_batch, bool) or not isinstance(max_batch, (int, np.integer)) or max_batch < 1:
         raise RuntimeError('detect_pyramid: max_batch=%r must be a positive integer' % (max_batch,))
     if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1 or len(sizes) * K > _MERGE_MAX_ROWS:
@@ -548,6 +683,8 @@ def detect_pyramid(net, images, sizes=(480, 720, 1080), K=10, nms_thresh=0.4, ma
     levels = resize._pad_resize_levels(dev, sizes)
     xform = [[resize.level_xform(im.size(0), im.size(1), s) for im in host] for s in sizes]
     graph = not net.training and os.environ.get('DBX_GRAPH', '1') != '0'
+    if tc is not None:
+        return _pyramid_thresh(net, levels, xform, B, tc[0], tc[1], nms_thresh, max_batch, graph, bool(with_levels))
     dc = 5 if net.KIND == 'DenseBox' else 13
     n = nl * K
     # one device buffer for the whole call: [B][n][dc] float64 rows, then [B][n + 1] int32 keep lists -- a single copy to the host

@@ -148,12 +148,14 @@ class _DenseBoxBase(nn.Module):
         from .decode import detect_batch_resized
         return detect_batch_resized(self, images, size, K, nms_thresh, max_batch, score_thresh, max_dets)
 
-    def detect_pyramid(self, images, sizes=(480, 720, 1080), K=10, nms_thresh=0.4, max_batch=32):
+    def detect_pyramid(self, images, sizes=(480, 720, 1080), K=10, nms_thresh=0.4, max_batch=32, score_thresh=None, max_dets=1024,
+                       with_levels=False):
         """detect_batch_resized() at every size of `sizes` with one resize launch, the rows of all levels merged in source-frame
         coordinates and ONE NMS per frame over their union on the device; a list of (dets[len(sizes) * K, 5|13], keep) in input
-        order (densebox_amd.decode.detect_pyramid)."""
+        order.  score_thresh: every pixel of every level above it is a row (at most max_dets per level) in the place of the top K
+        (densebox_amd.decode.detect_pyramid)."""
         from .decode import detect_pyramid
-        return detect_pyramid(self, images, sizes, K, nms_thresh, max_batch)
+        return detect_pyramid(self, images, sizes, K, nms_thresh, max_batch, score_thresh, max_dets, with_levels)
 
 
 class DenseBox(_DenseBoxBase):

@@ -52,8 +52,11 @@ const char* dbx_last_error(void);
  *  10  additions only: dbx_resize_job, dbx_resize_cubic_batch_u8, dbx_resize_batch_workspace_bytes (batched pad + bicubic resize)
  *  11  additions only: dbx_merge_xform, dbx_merge_nms_batch, dbx_merge_nms_batch_workspace_bytes (pyramid levels merged + one NMS per frame)
  *  12  additions only: dbx_detect_thresh_batch, dbx_detect_thresh_batch_scratch_bytes (score-threshold decode, packed results),
- *      dbx_nms_large, dbx_nms_large_scratch_bytes (greedy NMS for up to 4096 rows on many CUs) */
-#define DBX_ABI_VERSION 12
+ *      dbx_nms_large, dbx_nms_large_scratch_bytes (greedy NMS for up to 4096 rows on many CUs)
+ *  13  additions only: dbx_thresh_rows_batch, dbx_thresh_rows_batch_scratch_bytes (the threshold decode's rows without its NMS),
+ *      dbx_merge_nms_thresh_batch, dbx_merge_nms_thresh_batch_workspace_bytes (pyramid merge + NMS over per-level row counts that
+ *      stay on the device) */
+#define DBX_ABI_VERSION 13
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
 int dbx_device_arch(int device);
@@ -476,6 +479,19 @@ int dbx_detect_thresh_batch(const float* score, const float* loc, const float* l
                             int32_t batch, int32_t rows, int32_t cols, float score_thresh, int32_t max_dets, double nms_thresh,
                             double* dets, int32_t det_cols, int64_t* topk_idx, int32_t* keep, int32_t* counts, void* scratch,
                             void* stream);
+/* The select stage of dbx_detect_thresh_batch alone -- one launch, no suppression matrix, no sweep, no keep list -- for a caller that
+ * merges the rows of several runs before ONE NMS (dbx_merge_nms_thresh_batch).  Maps, score_thresh, max_dets, det_cols and the
+ * refusals are dbx_detect_thresh_batch's.  Outputs (device), in SLOT layout:
+ *   dets      [batch][max_dets][det_cols] float64: image b's n_b rows start at row b * max_dets; nothing beyond row n_b is written.
+ *   topk_idx  [batch][max_dets] likewise.
+ *   counts    int32 [batch][2]: (n_b, number of pixels above the threshold).
+ * Rows and indices are bit for bit the first n_b rows dbx_detect_thresh_batch writes for the same inputs (one device function).
+ * scratch: dbx_thresh_rows_batch_scratch_bytes(batch, rows, cols, max_dets) bytes (-1 for counts out of range), a non-null device
+ * pointer; this version works in LDS and does not write it. */
+int64_t dbx_thresh_rows_batch_scratch_bytes(int32_t batch, int32_t rows, int32_t cols, int32_t max_dets);
+int dbx_thresh_rows_batch(const float* score, const float* loc, const float* lm_heat, const float* lm_loc,
+                          int32_t batch, int32_t rows, int32_t cols, float score_thresh, int32_t max_dets,
+                          double* dets, int32_t det_cols, int64_t* topk_idx, int32_t* counts, void* scratch, void* stream);
 /* dbx_nms (DenseBox.py:3398-3443) for 1 <= n <= 4096 rows with the same keep list on every input (ties, NaN scores and boxes included):
  * a sort gives the order, the n x ceil(n / 64)-word suppression matrix is built by ceil(n / 64) workgroups, one wave walks it.
  * keep [n + 1]; scratch: dbx_nms_large_scratch_bytes(n) bytes (-1 outside 1..4096).  Refused: null pointers, n outside 1..4096,
@@ -503,6 +519,31 @@ typedef struct dbx_merge_xform { double scale, off_x, off_y; } dbx_merge_xform;
 int64_t dbx_merge_nms_batch_workspace_bytes(int32_t levels, int32_t batch, int32_t K);
 int dbx_merge_nms_batch(const double* const* level_dets, const dbx_merge_xform* xform, int32_t levels, int32_t batch, int32_t K,
                         int32_t det_cols, double nms_thresh, double* out_dets, int32_t* out_keep, void* workspace, void* stream);
+
+/* dbx_merge_nms_batch over VARIABLE row counts that never leave the device: level_dets[l] / level_counts[l] are what
+ * dbx_thresh_rows_batch(max_dets) wrote for level l of the same `batch` frames (HOST arrays of device pointers, copied into `workspace`
+ * like xform).  With n_(l,b) the count of level l, frame b -- read on the device, clamped to 0..max_dets, never trusted as a loop
+ * bound -- frame b's union has m_b = sum over l of n_(l,b) rows.  Three launches on `stream` whose grids depend on (levels, batch,
+ * max_dets) only; no host round trip, nothing polls.  Outputs (device), packed in dbx_detect_thresh_batch's style:
+ *   out_counts  int32 [batch][levels][2]: the level pairs of every frame (the clamped n, the pixels above the threshold), then
+ *               int32 [batch + 1]: P[b] = m_0 + ... + m_(b-1), P[batch] = the rows of the call.  2 * batch * levels + batch + 1 words.
+ *   out_dets    frame b's m_b rows start at row P[b], level by level in the order of the levels, mapped as dbx_merge_nms_batch maps
+ *               them (xform[l * batch + b]; column 4 copied; NaN passes through).  Capacity batch * levels * max_dets rows.
+ *   out_keep    frame b's list is m_b + 1 words at word P[b] + b: the count, then the kept row numbers within the frame's union in
+ *               the reference's order -- what dbx_nms_large returns on those m_b rows (score descending, the HIGHER union row first
+ *               among equal scores, !(ovr <= thresh) suppresses).  out_keep == (int32_t*)out_dets asks for the lists right BEHIND
+ *               the packed rows, at byte P[batch] * det_cols * 8 of out_dets: rows and lists are then
+ *               P[batch] * (det_cols * 8 + 4) + batch * 4 contiguous bytes.
+ * A frame with m_b == 0 writes its pairs, its prefix word and a zero list count, and nothing else.
+ * workspace: dbx_merge_nms_thresh_batch_workspace_bytes(levels, batch, max_dets) bytes (device records, and per frame the NMS order
+ * and the suppression matrix; -1 for counts out of range); it may be reused by the next call on the same stream.  Refused with
+ * DBX_ERR_ARG before anything is queued: a null pointer (any level pointer included), levels or batch below 1, max_dets outside
+ * 1..4096, levels * max_dets above 4096, det_cols other than 5 or 13, a scale that is not finite and positive, a non-finite offset,
+ * a NaN or negative nms_thresh. */
+int64_t dbx_merge_nms_thresh_batch_workspace_bytes(int32_t levels, int32_t batch, int32_t max_dets);
+int dbx_merge_nms_thresh_batch(const double* const* level_dets, const int32_t* const* level_counts, const dbx_merge_xform* xform,
+                               int32_t levels, int32_t batch, int32_t max_dets, int32_t det_cols, double nms_thresh,
+                               double* out_dets, int32_t* out_keep, int32_t* out_counts, void* workspace, void* stream);
 
 /* ---- plate rectification after decode (perspective_transform, DenseBox.py:3446-3481; OpenCV's published algorithm) ----
  * dbx_perspective_matrix: host function, cv2.getPerspectiveTransform: 3x3 row-major double map src -> dst of four (x, y)
