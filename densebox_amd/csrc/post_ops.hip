@@ -1207,34 +1207,63 @@ extern "C" int dbx_merge_nms_thresh_batch(const double* const* level_dets, const
 // PUBLISHED algorithm (imgwarp.cpp): 8x8 system in double solved by LU with partial pivoting; inverse map through the
 // 3x3 inverse; source coordinates rounded to 1/32 pixel (INTER_BITS = 5); 8-bit bilinear weights in 15-bit fixed point,
 // (sum + 2^14) >> 15.  Parity with OpenCV itself is unpinned; the GPU kernel is bit-exact against oracle/.
-extern "C" int dbx_perspective_matrix(const float* src_xy, const float* dst_xy, double* m9) {
-    DBX_REQUIRE(src_xy && dst_xy && m9, "perspective_matrix: null argument");
+// The 8x8 solve of cv2.getPerspectiveTransform on double corner values: false where a pivot fails the test.  One function for the host
+// entry point and the crop kernel, so both do the same operations in the same order.  Every index is a loop counter (the pivot row is
+// found by comparing the counter with piv), so the device copy keeps A in registers once the loops are unrolled.
+__host__ __device__ static inline bool perspective_solve(const double* s, const double* d, double* m9) {
     double A[8][9];
+#pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const double sx = src_xy[2 * i], sy = src_xy[2 * i + 1], dx = dst_xy[2 * i], dy = dst_xy[2 * i + 1];
+        const double sx = s[2 * i], sy = s[2 * i + 1], dx = d[2 * i], dy = d[2 * i + 1];
         const double r0[9] = {sx, sy, 1, 0, 0, 0, -sx * dx, -sy * dx, dx};
         const double r1[9] = {0, 0, 0, sx, sy, 1, -sx * dy, -sy * dy, dy};
+#pragma unroll
         for (int j = 0; j < 9; ++j) { A[i][j] = r0[j]; A[i + 4][j] = r1[j]; }
     }
+#pragma unroll
     for (int c = 0; c < 8; ++c) {                      // Gaussian elimination, partial pivoting (DECOMP_LU)
         int piv = c;
-        for (int r = c + 1; r < 8; ++r) if (fabs(A[r][c]) > fabs(A[piv][c])) piv = r;
-        DBX_REQUIRE(fabs(A[piv][c]) > 2.220446049250313e-16, "perspective_matrix: degenerate corner configuration");
-        if (piv != c) for (int j = 0; j < 9; ++j) { const double t = A[c][j]; A[c][j] = A[piv][j]; A[piv][j] = t; }
-        const double d = -1.0 / A[c][c];
+        double best = fabs(A[c][c]);
+#pragma unroll
         for (int r = c + 1; r < 8; ++r) {
-            const double f = A[r][c] * d;
+            const double v = fabs(A[r][c]);
+            if (v > best) { best = v; piv = r; }
+        }
+        if (!(best > 2.220446049250313e-16)) return false;
+#pragma unroll
+        for (int r = c + 1; r < 8; ++r) {
+            if (r == piv) {
+#pragma unroll
+                for (int j = 0; j < 9; ++j) { const double t = A[c][j]; A[c][j] = A[r][j]; A[r][j] = t; }
+            }
+        }
+        const double dd = -1.0 / A[c][c];
+#pragma unroll
+        for (int r = c + 1; r < 8; ++r) {
+            const double f = A[r][c] * dd;
+#pragma unroll
             for (int j = c + 1; j < 9; ++j) A[r][j] += f * A[c][j];
         }
     }
     double x[8];
+#pragma unroll
     for (int r = 7; r >= 0; --r) {
         double acc = A[r][8];
+#pragma unroll
         for (int j = r + 1; j < 8; ++j) acc -= A[r][j] * x[j];
         x[r] = acc / A[r][r];
     }
+#pragma unroll
     for (int i = 0; i < 8; ++i) m9[i] = x[i];
     m9[8] = 1.0;
+    return true;
+}
+
+extern "C" int dbx_perspective_matrix(const float* src_xy, const float* dst_xy, double* m9) {
+    DBX_REQUIRE(src_xy && dst_xy && m9, "perspective_matrix: null argument");
+    double s[8], d[8];
+    for (int i = 0; i < 8; ++i) { s[i] = src_xy[i]; d[i] = dst_xy[i]; }
+    DBX_REQUIRE(perspective_solve(s, d, m9), "perspective_matrix: degenerate corner configuration");
     return DBX_OK;
 }
 
@@ -1272,7 +1301,7 @@ __global__ void warp_perspective_u8_kernel(const WarpArgs a) {
 }
 
 // dst -> src map: the inverse of the 3x3 src -> dst map m, cofactor form in double.  False when the determinant is zero.
-static bool warp_inverse(const double* m, double* im) {
+__host__ __device__ static inline bool warp_inverse(const double* m, double* im) {
     const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
     if (det == 0.0) return false;
     const double d = 1.0 / det;
@@ -1430,6 +1459,141 @@ extern "C" int dbx_warp_perspective_batch_u8(const dbx_warp_job* jobs, int32_t n
         case 2: hipLaunchKernelGGL(warp_perspective_batch_u8_kernel<2>, grid, block, 0, (hipStream_t)stream, dj, dt, njobs); break;
         case 3: hipLaunchKernelGGL(warp_perspective_batch_u8_kernel<3>, grid, block, 0, (hipStream_t)stream, dj, dt, njobs); break;
         default: hipLaunchKernelGGL(warp_perspective_batch_u8_kernel<4>, grid, block, 0, (hipStream_t)stream, dj, dt, njobs); break;
+    }
+    DBX_LAUNCH_CHECK();
+    return DBX_OK;
+}
+
+// ---- fixed-size plate crops, rectified on the device (dbx_plate_crops_batch)
+// frames x slots crops of oh x ow pixels: a fixed grid, so the (frame, slot, tile) triple comes from blockIdx by division -- no prefix
+// table, no search.  Every workgroup of a slot solves the slot's homography itself: all lanes run perspective_solve on the same values
+// (the float32-rounded quad read from device memory -> the rectangle (0,0)..(ow-1,oh-1)), so there is no broadcast and no second
+// launch; the copies of the solve run side by side on different SIMDs and cost no wall time over solving it once.  Then the batched
+// warp's two passes, unchanged: 64 consecutive pixels per wave step into LDS, 16-byte / dword / byte stores by the slot's alignment.
+// Slots that are not ok (and slots past the frame's count) store zeros through the same path, so the call writes every byte of dst.
+struct PlateCropArgs {
+    const dbx_crop_frame* frames;
+    const double* quads;
+    const int* sel;
+    unsigned char* dst;
+    int* ok;
+    double* m9_out;
+    long long row_stride, frame_stride, npix;
+    int slots, ow, oh;
+    unsigned int tiles;                  // workgroups per slot
+};
+
+__host__ __device__ static inline bool finite_f64(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN and inf
+
+template <int C>
+__global__ __launch_bounds__(WARP_THREADS) void plate_crops_batch_u8_kernel(const PlateCropArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char seg[WARP_THREADS / 64][WARP_SEG * C];
+    const unsigned int t = blockIdx.x % a.tiles, slot = blockIdx.x / a.tiles;
+    const int j = (int)(slot % (unsigned int)a.slots), b = (int)(slot / (unsigned int)a.slots);
+    const int* S = a.sel ? a.sel + (size_t)b * (a.slots + 1) : nullptr;
+    const int count = S ? (S[0] < 0 ? 0 : (S[0] > a.slots ? a.slots : S[0])) : a.slots;
+    const dbx_crop_frame F = a.frames[b];
+    double m[9], im[9];
+    bool ok = j < count && F.src != nullptr && F.sh > 0 && F.sw > 0;
+    if (ok) {
+        const int r = S ? S[1 + j] : j;
+        ok = r >= 0 && (!S || (long long)r * a.row_stride + 8 <= a.frame_stride);     // a row of `sel` must lie inside its frame's stride
+        if (ok) {
+            const double* q = a.quads + (long long)b * a.frame_stride + (long long)r * a.row_stride;
+            double s[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                s[i] = (double)(float)q[i];            // np.float32(src_pts), widened again
+                ok = ok && finite_f64(s[i]);
+            }
+            const double W = (double)(float)(a.ow - 1), H = (double)(float)(a.oh - 1);
+            const double d[8] = {0.0, 0.0, W, 0.0, W, H, 0.0, H};
+            ok = ok && perspective_solve(s, d, m);
+            if (ok) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) ok = ok && finite_f64(m[i]);
+            }
+            ok = ok && warp_inverse(m, im);
+        }
+    }
+    if (t == 0 && threadIdx.x == 0) {
+        a.ok[slot] = ok ? 1 : 0;
+        if (ok && a.m9_out) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) a.m9_out[(size_t)slot * 9 + i] = m[i];
+        }
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long npix = a.npix;
+    const long long s0 = ((long long)t * (WARP_THREADS / 64) + wave) * WARP_SEG;                 // first pixel of the wave's segment
+    const int nseg = s0 >= npix ? 0 : (npix - s0 < WARP_SEG ? (int)(npix - s0) : WARP_SEG);       // its pixels (wave-uniform)
+    unsigned char* L = seg[wave];
+    if (nseg > 0) {
+        const warp_gsrc_t src = (warp_gsrc_t)F.src;
+        const int ow = a.ow;
+        const long long p = s0 + lane;
+        int y = (int)(p / ow), x = (int)(p - (long long)y * ow);
+#pragma unroll
+        for (int i = 0; i < WARP_PPT; ++i) {
+            const int q = i * 64 + lane;
+            if (q < nseg) {
+                const unsigned int px = ok ? warp_px_u8(im, src, F.sh, F.sw, C, x, y) : 0u;
+                if (C == 4) {
+                    reinterpret_cast<unsigned int*>(L)[q] = px;
+                } else {
+#pragma unroll
+                    for (int ch = 0; ch < C; ++ch) L[q * C + ch] = (unsigned char)(px >> (8 * ch));
+                }
+            }
+            x += 64;                                   // the lane's next pixel is 64 further on
+            if (x >= ow) { y += x / ow; x %= ow; }
+        }
+    }
+    __syncthreads();
+    if (nseg == 0) return;
+    const warp_gdst_t d = (warp_gdst_t)(a.dst + ((size_t)slot * (size_t)npix + (size_t)s0) * C);
+    const int nb = nseg * C;
+    const size_t al = (size_t)d;
+    for (int k = lane; 16 * k < nb; k += 64) {
+        const int b0 = 16 * k;
+        if (b0 + 16 <= nb && al % 16 == 0) {
+            reinterpret_cast<warp_gdst4_t>(d)[k] = reinterpret_cast<const u32x4*>(L)[k];
+        } else if (b0 + 16 <= nb && al % 4 == 0) {
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) reinterpret_cast<warp_gdst1_t>(d)[4 * k + jj] = reinterpret_cast<const unsigned int*>(L)[4 * k + jj];
+        } else {
+            for (int jj = b0; jj < nb && jj < b0 + 16; ++jj) d[jj] = L[jj];
+        }
+    }
+}
+
+extern "C" int dbx_plate_crops_batch(const dbx_crop_frame* frames, int32_t nframes, int32_t c, const double* quads, int64_t row_stride,
+                                     int64_t frame_stride, const int32_t* sel, int32_t slots, int32_t ow, int32_t oh, uint8_t* dst,
+                                     int32_t* ok, double* m9_out, void* stream) {
+    DBX_REQUIRE(nframes >= 0, "plate_crops_batch: nframes=%d is negative", nframes);
+    DBX_REQUIRE(c >= 1 && c <= 4, "plate_crops_batch: c=%d must be 1..4", c);
+    DBX_REQUIRE(slots >= 1, "plate_crops_batch: slots=%d must be positive", slots);
+    DBX_REQUIRE(ow >= 1 && oh >= 1, "plate_crops_batch: crop size %d x %d must be positive", ow, oh);
+    DBX_REQUIRE(row_stride >= 8, "plate_crops_batch: row_stride=%lld holds no quad of 8 values", (long long)row_stride);
+    DBX_REQUIRE(sel || frame_stride >= (int64_t)slots * row_stride, "plate_crops_batch: frame_stride=%lld is below slots * row_stride = %lld",
+                (long long)frame_stride, (long long)slots * (long long)row_stride);
+    if (nframes == 0) return DBX_OK;
+    DBX_REQUIRE(frames && quads && dst && ok, "plate_crops_batch: null argument");
+    constexpr long long tile = (long long)WARP_THREADS * WARP_PPT;        // pixels per workgroup
+    PlateCropArgs a;
+    a.npix = (long long)oh * ow;
+    const long long tiles = (a.npix + tile - 1) / tile, nslots = (long long)nframes * slots;
+    // one workgroup per tile, and a grid holds at most 2^32 - 1 work-items per dimension
+    DBX_REQUIRE(tiles <= 0xffffffffLL / WARP_THREADS / nslots, "plate_crops_batch: %lld slots of %lld tiles exceed the %lld tiles of one grid", nslots,
+                tiles, 0xffffffffLL / WARP_THREADS);
+    a.frames = frames; a.quads = quads; a.sel = sel; a.dst = dst; a.ok = ok; a.m9_out = m9_out;
+    a.row_stride = row_stride; a.frame_stride = frame_stride; a.slots = slots; a.ow = ow; a.oh = oh; a.tiles = (unsigned int)tiles;
+    const dim3 grid((unsigned)(tiles * nslots)), block(WARP_THREADS);
+    switch (c) {
+        case 1: hipLaunchKernelGGL(plate_crops_batch_u8_kernel<1>, grid, block, 0, (hipStream_t)stream, a); break;
+        case 2: hipLaunchKernelGGL(plate_crops_batch_u8_kernel<2>, grid, block, 0, (hipStream_t)stream, a); break;
+        case 3: hipLaunchKernelGGL(plate_crops_batch_u8_kernel<3>, grid, block, 0, (hipStream_t)stream, a); break;
+        default: hipLaunchKernelGGL(plate_crops_batch_u8_kernel<4>, grid, block, 0, (hipStream_t)stream, a); break;
     }
     DBX_LAUNCH_CHECK();
     return DBX_OK;

@@ -126,7 +126,10 @@ def _graph_replay(net, tag, image, K, nms_thresh, eager, to_host=True):
 
     to_host='second' (detect_batch_thresh's entries, K = (max_dets, score_thresh)): only the second result, the counts, is copied
     by the graph; the first, the packed arena, is returned as the entry's device tensor -- how much of it to fetch depends on the
-    counts, and a copy of a size that depends on device data cannot be a graph node."""
+    counts, and a copy of a size that depends on device data cannot be a graph node.
+
+    eager may return more than two tensors (detect_plate_crops' entries, K = (K, ow, oh, crops to the host)); to_host is then a
+    tuple with one flag per result -- copied to pinned memory by the graph, or returned as the entry's device tensor."""
     import collections
     cache = net.__dict__.setdefault('_detect_graphs', collections.OrderedDict())
     # weight signature: versions + storage addresses of every parameter (a replay reads the packed copies made at capture).
@@ -147,12 +150,11 @@ def _graph_replay(net, tag, image, K, nms_thresh, eager, to_host=True):
     if ent is None or ent[0] != sig:
         static_in = image.clone()
         for _ in range(2):                       # warm: workspace plan, packed weights, scratch buffers, kernel attributes
-            wd, wk = eager(net, static_in, K, nms_thresh)
-        h_dets = h_keep = None
-        if to_host:
-            if to_host != 'second':
-                h_dets = torch.empty(wd.shape, dtype=wd.dtype).pin_memory()    # (pinned allocation is not capturable)
-            h_keep = torch.empty(wk.shape, dtype=wk.dtype).pin_memory()
+            warm = eager(net, static_in, K, nms_thresh)
+        flags = to_host if isinstance(to_host, tuple) else (to_host is True, bool(to_host))      # True: both; 'second': the second
+        assert len(flags) == len(warm)
+        pinned = tuple(torch.empty(w.shape, dtype=w.dtype).pin_memory() if f else None       # (pinned allocation is not capturable)
+                       for w, f in zip(warm, flags))
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         # No cyclic garbage collection DURING the capture: a dead network (modules sit in reference cycles) takes its cached graphs
@@ -164,31 +166,30 @@ def _graph_replay(net, tag, image, K, nms_thresh, eager, to_host=True):
         gc.disable()
         try:
             with torch.cuda.graph(g):
-                dets, keep = eager(net, static_in, K, nms_thresh)
-                # the two result copies are graph nodes too (pinned destinations): one replay + one stream sync per call
+                outs = tuple(eager(net, static_in, K, nms_thresh))
+                # the result copies are graph nodes too (pinned destinations): one replay + one stream sync per call
                 # instead of two blocking .cpu() calls with their launch round trips (~60 us of idle GPU per call)
-                if to_host:
-                    if h_dets is not None:
-                        h_dets.copy_(dets, non_blocking=True)
-                    h_keep.copy_(keep, non_blocking=True)
+                for h, o in zip(pinned, outs):
+                    if h is not None:
+                        h.copy_(o, non_blocking=True)
         finally:
             if gc_was_on:
                 gc.enable()
         # The captured kernels hold RAW pointers into the engine's workspace plan and packed / folded weight buffers.  The
         # engine keeps one plan and re-creates its weight caches when the dtype or mode flips, so the entry pins every
         # tensor it captured: a later forward at another shape (or a train-mode step) cannot free what a replay reads.
-        ent = (sig, g, static_in, dets, keep, net._engine.captured_refs(), h_dets, h_keep)
+        ent = (sig, g, static_in, outs, net._engine.captured_refs(), pinned)
         cache[key] = ent
         while len(cache) > _MAX_GRAPHS:            # bounded: one graph + private pool + pinned workspace per shape
             cache.popitem(last=False)
     cache.move_to_end(key)
-    _, g, static_in, dets, keep, _refs, h_dets, h_keep = ent
+    _, g, static_in, outs, _refs, pinned = ent
     static_in.copy_(image)
     g.replay()
     if not to_host:
-        return dets, keep
+        return outs
     torch.cuda.current_stream().synchronize()
-    return (dets if h_dets is None else h_dets), h_keep
+    return tuple(o if h is None else h for o, h in zip(outs, pinned))
 
 
 def detect(net, image, K=10, nms_thresh=0.4):
@@ -440,6 +441,89 @@ def detect_plates(net, images, K=10, nms_thresh=0.4, max_batch=32, *, region, sc
     quads = [[[[d[k, 5], d[k, 6]], [d[k, 7], d[k, 8]], [d[k, 9], d[k, 10]], [d[k, 11], d[k, 12]]] for k in keep] for d, keep in res]
     plates = rectify._warp_batch(dev, kinds, quads, region)
     return [(d, keep, p) for (d, keep), p in zip(res, plates)]
+
+
+def _plate_crops_eager():
+    """The eager function of detect_plate_crops' chunks: forward, dbx_detect_batch, dbx_plate_crops_batch -> (dets, keep, crops, ok,
+    frame table) device tensors.  The crop launch reads the pixels of `images` (the graph's static input under capture), the quads at
+    dets + 5 and the kept rows in keep.  The frame table is the one thing that comes from the host: it is uploaded on the first call for
+    a tensor (the warm-up, outside the capture) and reused for the same address afterwards; the graph entry keeps it with the results."""
+    from . import rectify
+    tables = {}
+
+    def eager(net, images, kt, nms_thresh):
+        K, ow, oh = kt[:3]
+        dets, keep = _detect_batch_eager(net, images, K, nms_thresh)
+        B, dc = int(dets.size(0)), int(dets.size(2))
+        key = (images.data_ptr(), tuple(images.shape))
+        table = tables.get(key)
+        if table is None:
+            table = tables[key] = rectify.frame_table(list(images.unbind(0)))
+        crops, ok = rectify._crops_launch(table, B, 3, dets.data_ptr() + 5 * 8, dc, K * dc, keep, K, ow, oh, images.device)
+        return dets, keep, crops, ok, table
+    return eager
+
+
+def _plate_crops_chunk(net, x, K, ow, oh, nms_thresh, host_crops):
+    import os
+    x = (x if x.is_cuda else x.cuda()).contiguous()
+    kt = (K, ow, oh, host_crops)
+    if not net.training and os.environ.get('DBX_GRAPH', '1') != '0':
+        d, k, crops, ok, _ = _graph_replay(net, 'plate_crops', x, kt, nms_thresh, _plate_crops_eager(),
+                                           to_host=(True, True, host_crops, True, False))
+    else:
+        d, k, crops, ok, _ = _plate_crops_eager()(net, x, kt, nms_thresh)
+        d, k, ok = d.cpu(), k.cpu(), ok.cpu()
+        crops = crops.cpu() if host_crops else crops
+    d, k, ok = d.numpy(), k.numpy(), ok.numpy()
+    out = []
+    for b in range(d.shape[0]):
+        n = int(k[b, 0])
+        # every result owns its memory (a graph entry's buffers are overwritten by its next replay): crops by a clone, device to device
+        # for CUDA frames
+        out.append((d[b].copy(), [int(v) for v in k[b, 1:1 + n]], crops[b, :n].clone(), ok[b, :n] != 0))
+    return out
+
+
+def detect_plate_crops(net, images, *, size, K=10, nms_thresh=0.4, max_batch=32):
+    """detect_batch, then every kept detection's plate rectified to ONE crop size on the device -- the input of a plate recogniser --
+    with no host work between the decode and the warp: per chunk of at most `max_batch` same-shape frames the forward, dbx_detect_batch
+    and ONE dbx_plate_crops_batch launch, which reads the frames' pixels, the quads in columns 5..12 of the rows and the kept rows in
+    `keep` where the decode left them and solves the homographies itself (rectify.plate_crops_batch has the semantics).
+
+    images: uint8 frames only -- a [B,H,W,3] tensor or a list of [H,W,3] images (numpy arrays or tensors) of any sizes, as for
+    detect_plates; each is uploaded at most once.  net: DenseBoxLM or DenseBoxLMLOC.  size: (width, height) of a crop, e.g. (94, 24),
+    or one integer for both.  K, nms_thresh, max_batch, chunking and list grouping: detect_batch's.
+
+    Returns, per image in input order, (dets, keep, crops, ok): detect_batch's (dets, keep) bit for bit; crops uint8
+    [len(keep), oh, ow, 3] of the kind of the frame (numpy array, CPU tensor or CUDA tensor), crop j the rectification of row keep[j]
+    onto rectify.plate_rectangle(size); ok a numpy bool [len(keep)], False (and the crop all zeros) where the quad is degenerate or not
+    finite -- where detect_plates gives None.  Every result owns its memory.
+
+    Eval mode replays ONE hipGraph per chunk from the cache detect() uses, under a tag of its own, keyed by (batch shape, dtype,
+    (K, ow, oh, crops to the host), nms_thresh, compute dtype): the forward, the decode, the crop launch and the copies of dets, keep,
+    ok -- and of the crops, when the frames came from the host -- to pinned memory; one replay and one stream synchronise per chunk.
+    Train mode and DBX_GRAPH=0 run the same three steps eagerly.
+
+    There is no score_thresh here: the threshold decode has up to 4096 rows per image, and fixed slots for that many are a different
+    design (most of them empty, or a compaction pass); use detect_batch_thresh and rectify.plate_crops_batch for it."""
+    from . import rectify
+    ow, oh = rectify._crop_size('detect_plate_crops', size)
+    if net.KIND == 'DenseBox':
+        raise RuntimeError('detect_plate_crops: DenseBox rows have no landmarks to rectify; use DenseBoxLM or DenseBoxLMLOC')
+    host, kinds = rectify.host_images('detect_plate_crops', images, 3)
+    host_crops = any(k != 'cuda' for k in kinds)
+    if torch.is_tensor(images):                    # one upload of the batch; the forward and the warp read the same device copy
+        x = (images if images.is_cuda else images.cuda()).contiguous()
+    else:
+        x = rectify.to_device(images, host)
+    res = _detect_many('detect_plate_crops', x, max_batch, lambda c: _plate_crops_chunk(net, c, K, ow, oh, nms_thresh, host_crops))
+    out = []
+    for (d, keep, crops, ok), kind in zip(res, kinds):
+        if kind == 'cuda':
+            crops = crops if crops.is_cuda else crops.cuda()         # (a CUDA frame in a list that also holds host frames)
+        out.append((d, keep, crops.numpy() if kind == 'numpy' else crops, ok))
+    return out
 
 
 def detect_batch_resized(net, images, size=720, K=10, nms_thresh=0.4, max_batch=32, score_thresh=None, max_dets=1024):

@@ -142,6 +142,12 @@ class _DenseBoxBase(nn.Module):
         from .decode import detect_plates
         return detect_plates(self, images, K, nms_thresh, max_batch, region=region, score_thresh=score_thresh, max_dets=max_dets)
 
+    def detect_plate_crops(self, images, *, size, K=10, nms_thresh=0.4, max_batch=32):
+        """detect_batch() on uint8 frames, then every kept detection's plate rectified to one crop size on the device, in the same
+        hipGraph: a list of (dets, keep, crops [len(keep), oh, ow, 3], ok) in input order (densebox_amd.decode.detect_plate_crops)."""
+        from .decode import detect_plate_crops
+        return detect_plate_crops(self, images, size=size, K=K, nms_thresh=nms_thresh, max_batch=max_batch)
+
     def detect_batch_resized(self, images, size=720, K=10, nms_thresh=0.4, max_batch=32, score_thresh=None, max_dets=1024):
         """detect_batch() on uint8 frames of any sizes, each padded to a square and resized to size x size in one launch; a list of
         (dets, keep) in input order, coordinates mapped back to the source frames (densebox_amd.decode.detect_batch_resized)."""

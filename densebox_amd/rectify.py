@@ -207,3 +207,105 @@ def _warp_batch(dev, kinds, quads, region):
         v = src[off:off + oh * ow * c].view(oh, ow, c)
         out[b][j] = v.numpy() if kinds[b] == 'numpy' else v
     return out
+
+
+# ---------------------------------------------------------------------------------------------- fixed-size plate crops
+def _crop_size(who, size):
+    """(ow, oh) of a crop size given as an integer or (width, height): resize._check_size's rules, and a sequence holds exactly two."""
+    from .resize import _check_size
+    if not isinstance(size, (int, np.integer)) or isinstance(size, (bool, np.bool_)):
+        try:
+            n = len(size)
+        except TypeError:
+            n = -1
+        if n != 2:
+            raise RuntimeError('%s: size must be an integer or (width, height), got %r' % (who, size))
+    return _check_size(who, size)
+
+
+def plate_rectangle(size):
+    """The four destination corners of a crop of size = (width, height): (0,0), (w-1,0), (w-1,h-1), (0,h-1) -- the corners of the quad
+    land on the centres of the first and last pixel, as dst_rectangle's do on the canvas."""
+    w, h = _crop_size('plate_rectangle', size)
+    return [[0, 0], [w - 1, 0], [w - 1, h - 1], [0, h - 1]]
+
+
+def frame_table(dev):
+    """The device table of dbx_crop_frame records {src, sh, sw} of contiguous uint8 [H,W,C] CUDA tensors (one small upload).  It holds
+    raw addresses: keep `dev` alive while the table is in use."""
+    rec = (_lib.CropFrame * len(dev))()
+    for r, im in zip(rec, dev):
+        r.src, r.sh, r.sw = im.data_ptr(), int(im.size(0)), int(im.size(1))
+    return torch.frombuffer(rec, dtype=torch.uint8).to(dev[0].device)
+
+
+def _crops_launch(table, nframes, c, quads_ptr, row_stride, frame_stride, sel, slots, ow, oh, device, with_m9=False):
+    """ONE dbx_plate_crops_batch launch on the current stream: (crops uint8 [nframes, slots, oh, ow, c], ok int32 [nframes, slots][, m9
+    float64 [nframes, slots, 9]]) device tensors.  Nothing is copied from the host and nothing waits, so a graph capture may hold it."""
+    crops = torch.empty((nframes, slots, oh, ow, c), dtype=torch.uint8, device=device)
+    ok = torch.empty((nframes, slots), dtype=torch.int32, device=device)
+    m9 = torch.empty((nframes, slots, 9), dtype=torch.float64, device=device) if with_m9 else None
+    check(_lib.lib().dbx_plate_crops_batch(C.c_void_p(table.data_ptr()), nframes, c, C.c_void_p(quads_ptr), row_stride, frame_stride,
+                                           _lib.ptr(sel), slots, ow, oh, C.c_void_p(crops.data_ptr()), C.c_void_p(ok.data_ptr()),
+                                           _lib.ptr(m9), stream_ptr()))
+    return (crops, ok, m9) if with_m9 else (crops, ok)
+
+
+def _quad_rows(who, b, qs):
+    """quads[b] as a float64 [Q_b, 8] array: a list of 4-point quads, or a [Q_b, 8] / [Q_b, 4, 2] array or tensor."""
+    if torch.is_tensor(qs):
+        qs = qs.detach().cpu().numpy()
+    try:
+        a = np.asarray(qs, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise RuntimeError('%s: quads[%d] must hold quads of 8 numbers (4 (x, y) points), got %r' % (who, b, qs))
+    if a.size == 0 and a.ndim <= 1:
+        return np.zeros((0, 8), dtype=np.float64)
+    if not ((a.ndim == 2 and a.shape[1] == 8) or (a.ndim == 3 and a.shape[1:] == (4, 2))):
+        raise RuntimeError('%s: quads[%d] must hold quads of 8 numbers (4 (x, y) points), got shape %s' % (who, b, list(a.shape)))
+    return np.ascontiguousarray(a.reshape(a.shape[0], 8))
+
+
+def plate_crops_batch(images, quads, *, size):
+    """Every quad of every image rectified to ONE crop size in ONE launch (dbx_plate_crops_batch): the input a plate recogniser takes.
+
+    images: as for perspective_transform_batch (a uint8 [B,H,W,C] tensor or a list of uint8 [H,W,C] images of any sizes, numpy or
+    torch, CPU or GPU; C is 1..4 and the same for all); each image is uploaded at most once.  quads[b]: the quads (left-up, right-up,
+    right-down, left-down) of image b -- a list of 4-point quads, or a float [Q_b, 8] or [Q_b, 4, 2] array or tensor.  size: (width,
+    height) of a crop, or one integer for both.  The quads travel to the device padded to the largest Q_b, with a count per image,
+    next to the frame table; the homographies are solved there (dbx_perspective_matrix's solve, compiled for the device) onto
+    plate_rectangle(size).
+
+    Returns per image (crops, ok): crops uint8 [Q_b, oh, ow, C] of the image's kind (CUDA tensors are views into one device arena;
+    numpy arrays and CPU tensors come from one download of it), ok a numpy bool [Q_b].  Crop j is bit for bit
+    warp_perspective(image, get_perspective_matrix(quad, plate_rectangle(size)), size) where ok[j]; it is all zeros where not:
+    degenerate corners, a coordinate that is not finite in float32, a singular map -- the cases perspective_transform_batch gives
+    None for."""
+    who = 'plate_crops_batch'
+    ow, oh = _crop_size(who, size)
+    host, kinds = host_images(who, images, None)
+    if len(quads) != len(host):
+        raise RuntimeError('%s: %d lists of quads for %d images' % (who, len(quads), len(host)))
+    rows = [_quad_rows(who, b, qs) for b, qs in enumerate(quads)]
+    B, c, slots = len(host), int(host[0].size(2)), max(len(r) for r in rows)
+    if slots == 0:
+        ok = torch.zeros((B, 0), dtype=torch.int32)
+        crops = [torch.zeros((0, oh, ow, c), dtype=torch.uint8) for _ in range(B)]
+        crops = [cr.cuda() if k == 'cuda' else cr for cr, k in zip(crops, kinds)]
+    else:
+        packed = np.zeros((B, slots, 8), dtype=np.float64)
+        sel = np.zeros((B, slots + 1), dtype=np.int32)
+        for b, r in enumerate(rows):
+            packed[b, :len(r)] = r
+            sel[b, 0] = len(r)
+            sel[b, 1:1 + len(r)] = np.arange(len(r))
+        dev = to_device(images, host)
+        device = dev[0].device
+        d_quads, d_sel = torch.from_numpy(packed).to(device), torch.from_numpy(sel).to(device)
+        table = frame_table(dev)
+        arena, ok = _crops_launch(table, B, c, d_quads.data_ptr(), 8, slots * 8, d_sel, slots, ow, oh, device)
+        down = arena.cpu() if any(k != 'cuda' for k in kinds) else None
+        crops = [(arena if k == 'cuda' else down)[b, :len(rows[b])] for b, k in enumerate(kinds)]
+        ok = ok.cpu()                                          # (behind the launch on the stream: dev and table are done with)
+    ok = ok.numpy() != 0
+    return [(cr.numpy() if k == 'numpy' else cr, ok[b, :len(rows[b])].copy()) for b, (cr, k) in enumerate(zip(crops, kinds))]

@@ -55,7 +55,10 @@ const char* dbx_last_error(void);
  *      dbx_nms_large, dbx_nms_large_scratch_bytes (greedy NMS for up to 4096 rows on many CUs)
  *  13  additions only: dbx_thresh_rows_batch, dbx_thresh_rows_batch_scratch_bytes (the threshold decode's rows without its NMS),
  *      dbx_merge_nms_thresh_batch, dbx_merge_nms_thresh_batch_workspace_bytes (pyramid merge + NMS over per-level row counts that
- *      stay on the device) */
+ *      stay on the device)
+ *      also at 13, without a bump: dbx_crop_frame, dbx_plate_crops_batch (fixed-size plate crops rectified on the device).  A pure
+ *      addition changes no layout, argument list or scratch contract, so a binding written against 13 stays valid; a binding that needs
+ *      the new entry point looks the symbol up */
 #define DBX_ABI_VERSION 13
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
@@ -571,6 +574,38 @@ typedef struct dbx_warp_job {
 } dbx_warp_job;
 int64_t dbx_warp_batch_workspace_bytes(int32_t njobs);
 int dbx_warp_perspective_batch_u8(const dbx_warp_job* jobs, int32_t njobs, int32_t c, uint8_t* dst, void* workspace, void* stream);
+
+/* Fixed-size plate crops, rectified on the device: one launch over nframes x slots crops of oh x ow pixels, with no host work between
+ * the decode and the warp.  Everything the launch reads is on the DEVICE or passed by value; the call copies nothing from the host and
+ * never synchronises, so it can be captured into a hipGraph behind dbx_detect_batch.
+ *   frames      device table of nframes records {src, sh, sw}: interleaved uint8 images [sh][sw][c] of any sizes (the caller uploads it)
+ *   quads       device float64; the 8 values (x_lu, y_lu, x_ru, y_ru, x_rd, y_rd, x_ld, y_ld) of row r of frame b are at
+ *               quads + b * frame_stride + r * row_stride (strides in doubles).  Detection rows: dets + 5, row_stride 13,
+ *               frame_stride K * 13
+ *   sel         device int32 [nframes][slots + 1] in dbx_detect_batch's `keep` layout: the count, then the row indices in that order
+ *               (slot j is row sel[b][1 + j]); NULL: rows 0..slots-1.  A count is clamped to 0..slots; a row index that is negative or
+ *               whose quad does not end inside the frame's stride (r * row_stride + 8 > frame_stride) makes the slot not ok
+ *   dst         device uint8 [nframes][slots][oh][ow][c]; ok: device int32 [nframes][slots]
+ *   m9_out      optional device float64 [nframes][slots][9] (may be NULL): the forward matrix of every slot that is ok; entries of
+ *               other slots are not written
+ * Slot (b, j) with j below the count: every coordinate is rounded to float32 and widened again; the map is dbx_perspective_matrix's
+ * solve (the same function, compiled for the device) from the quad to the rectangle (0,0), (ow-1,0), (ow-1,oh-1), (0,oh-1) as float32
+ * values (corners on the centres of the first and last pixel); its inverse and every pixel are dbx_warp_perspective_u8's, so a crop is
+ * bit for bit dbx_warp_perspective_u8(src, sh, sw, c, m9, ., oh, ow) with the host's m9.  A slot is NOT ok (ok = 0, crop all zeros)
+ * when a float32 coordinate is not finite, a pivot fails dbx_perspective_matrix's test, an entry of the matrix is not finite, the
+ * cofactor determinant is 0.0, or its frame record has a null src or a non-positive size; so are the slots past the count.  The call
+ * writes every byte of dst and every word of ok (16-byte words where a slot's address allows, dwords or bytes otherwise) and nothing
+ * outside them.  It needs no workspace.
+ * Refused with DBX_ERR_ARG before anything is queued: nframes < 0, c outside 1..4, slots < 1, ow or oh < 1, row_stride < 8,
+ * frame_stride < slots * row_stride when sel is NULL, a null frames / quads / dst / ok, more tiles than one grid holds (2^24 - 1
+ * workgroups of 2048 pixels, ceil(oh * ow / 2048) per slot).  nframes == 0: no-op. */
+typedef struct dbx_crop_frame {
+    const uint8_t* src;      /* device image [sh][sw][c] */
+    int32_t sh, sw;
+} dbx_crop_frame;
+int dbx_plate_crops_batch(const dbx_crop_frame* frames, int32_t nframes, int32_t c, const double* quads, int64_t row_stride,
+                          int64_t frame_stride, const int32_t* sel, int32_t slots, int32_t ow, int32_t oh, uint8_t* dst, int32_t* ok,
+                          double* m9_out, void* stream);
 
 /* ---- batched pad + bicubic resize (pad_img + cv2.resize(..., INTER_CUBIC), DenseBox.py:1282-1340; the patch cutters' resize of a
  * cropped window) ----
