@@ -96,26 +96,18 @@ __device__ __forceinline__ void block_argmax_g(const float* vals, int n, float* 
     __syncthreads();
 }
 
-// the same reduction over one cached (value, index) candidate per thread
-__device__ __forceinline__ void block_argmax_cached(float bv, int bi, float* red_v, int* red_i, float& ov, int& oi) {
+// Block-wide maximum of one 64-bit composite per thread (0 = no candidate), for the top-K rounds: a wave reduction by shuffles, the 16
+// wave maxima through red_c, every thread reads all of them.  One barrier inside; the caller puts one between two calls (red_c).
+__device__ __forceinline__ unsigned long long block_max_comp(unsigned long long c, unsigned long long* red_c) {
     const int tid = threadIdx.x;
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float v2 = __shfl_down(bv, off); const int i2 = __shfl_down(bi, off);
-        if (i2 != 0x7fffffff && (bi == 0x7fffffff || v2 > bv || (v2 == bv && i2 < bi))) { bv = v2; bi = i2; }
-    }
-    if ((tid & 63) == 0) { red_v[tid >> 6] = bv; red_i[tid >> 6] = bi; }
+    for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(c, off); c = o > c ? o : c; }
+    if ((tid & 63) == 0) red_c[tid >> 6] = c;
     __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < DET_THREADS / 64; ++w) {
-            const float v2 = red_v[w]; const int i2 = red_i[w];
-            if (i2 != 0x7fffffff && (bi == 0x7fffffff || v2 > bv || (v2 == bv && i2 < bi))) { bv = v2; bi = i2; }
-        }
-        red_v[0] = bv; red_i[0] = bi;
-    }
-    __syncthreads();
-    ov = red_v[0]; oi = red_i[0];
-    __syncthreads();
+    c = red_c[0];
+#pragma unroll
+    for (int w = 1; w < DET_THREADS / 64; ++w) { const unsigned long long o = red_c[w]; c = o > c ? o : c; }
+    return c;
 }
 
 // greedy NMS over dets[n][dc] (float64): keep list in `keep` (keep[0] = count).  order = score descending, ties by
@@ -251,7 +243,7 @@ __device__ void nms_block(const double* dets, int n, int dc, double thresh, int*
 struct DetArgs {
     const float* score; const float* loc; const float* lm_heat; const float* lm_loc;
     int rows, cols, K, dc; double thresh;
-    double* dets; long long* topk; int* keep; float* work; int* order; unsigned char* supp; unsigned long long* mask;
+    double* dets; long long* topk; int* keep; unsigned* work; int* order; unsigned char* supp; unsigned long long* mask;
     long long scratch_stride;
 };
 
@@ -344,12 +336,21 @@ __device__ __forceinline__ void det_radix_select(const float* score, int n, int 
     }
 }
 
-// top-K by radix select + sort from this K on; below it the arg-max rounds over the two-level LDS structure are faster (same-box
+// detect_kernel's top-K: ONE order on every path -- the descending order of the (det_key << 32 | ~index) composites: larger score
+// first, lower index on ties, -0 == +0, -inf above NaN, NaN below every number with the lower index first, no index twice -- and five
+// paths chosen from (K, n = rows * cols):
+//   1  register tournament                                  K <= 48 and n <= 16384
+//   2  radix select + bitonic sort                          DET_SELECT_MIN_K <= K <= 1024, any n
+//   3  rounds, working copy in LDS, bucket maxima in LDS    K > 1024 and n <= 16384
+//   4  rounds, working copy in global scratch, buckets      (K <= 48 or K > 1024) and 16384 < n <= 262144 (4096 buckets of 64)
+//   5  rounds, flat per-thread rescan of the global copy    (K <= 48 or K > 1024) and n > 262144
+// tests/test_hip_topk_paths.py holds every path to NumPy's order on both sides of every switch.
+// Radix select + sort from DET_SELECT_MIN_K on; below it the rounds over the two-level LDS structure are faster (same-box
 // A/B at K = 10 on a 128 x 128 map: whole 512 x 512 detect() 0.486 ms with rounds, 0.506 ms with select + a 16-element sort).
 #ifndef DET_SELECT_MIN_K
 #define DET_SELECT_MIN_K 49
 #endif
-// one workgroup per image (blockIdx.x): the same three top-K paths, tie order, NaN handling and NMS on every image of the batch
+// one workgroup per image (blockIdx.x): the same top-K paths, tie order, NaN handling and NMS on every image of the batch
 __global__ __launch_bounds__(DET_THREADS) void detect_kernel(const DetArgs a0) {
     DetArgs a = a0;
     {
@@ -362,7 +363,7 @@ __global__ __launch_bounds__(DET_THREADS) void detect_kernel(const DetArgs a0) {
         a.topk += b * a0.K;
         a.keep += b * (a0.K + 1);
         const size_t so = b * (size_t)a0.scratch_stride;
-        a.work = (float*)((char*)a0.work + so);
+        a.work = (unsigned*)((char*)a0.work + so);
         a.order = (int*)((char*)a0.order + so);
         a.supp = a0.supp + so;
         if (a.mask) a.mask = (unsigned long long*)((char*)a0.mask + so);
@@ -372,8 +373,8 @@ __global__ __launch_bounds__(DET_THREADS) void detect_kernel(const DetArgs a0) {
     __shared__ int lm_arg[4];
     const int tid = threadIdx.x, n = a.rows * a.cols;
     constexpr int BK = 64, NB_MAX = 4096;
-    __shared__ float bmax[NB_MAX];
-    __shared__ int bidx[NB_MAX];
+    __shared__ unsigned long long bcomp[NB_MAX];                 // bucket maxima of the rounds; the candidates of the other two paths
+    __shared__ unsigned det_hist[256];
     // landmark arg-max per heat-map channel (parse_DetLM, DenseBox.py:3284-3292): identical for every detection
     if (a.lm_heat && !a.lm_loc) {
         for (int j = 0; j < 4; ++j) {
@@ -391,8 +392,8 @@ __global__ __launch_bounds__(DET_THREADS) void detect_kernel(const DetArgs a0) {
         // as (key << 32 | ~index) composites -- larger composite = larger score, lower index on ties, the select path's order -- each
         // wave extracts ITS top K by K rounds of a register maximum + a wave reduction (shuffles only, no workgroup barrier), the 16
         // waves leave their sorted lists in LDS and wave 0 merges the 16 K candidates the same way: ~6 us instead of K block-wide
-        // arg-max rounds with three barriers each (30 us at K = 10).
-        unsigned long long* wcand = (unsigned long long*)bidx;            // [16][48]
+        // rounds with their barriers (measured when a round had three: 30 us at K = 10).
+        unsigned long long* wcand = bcomp;                                 // [16][48]
         const int lane = tid & 63, wv = tid >> 6;
         unsigned long long comp[16];
 #pragma unroll
@@ -438,9 +439,8 @@ __global__ __launch_bounds__(DET_THREADS) void detect_kernel(const DetArgs a0) {
         // K in (48, 1024] (round 3: K = 1000 at 1080p took 4.7 ms as 1000 arg-max rounds): radix select of the K-th largest key
         // (four 8-bit passes, LDS histogram), compaction of the keys above it plus the lowest-index ties, bitonic sort of <= 1024
         // (key, index) pairs in LDS -- ~0.1 ms, the same ranking bit for bit.
-        unsigned* hist = (unsigned*)bmax;                        // [256]
-        unsigned long long* cand = (unsigned long long*)bidx;    // [1024] (key << 32) | ~index: descending sort = reference order
-        det_radix_select(a.score, n, a.K, hist, cand);
+        unsigned long long* cand = bcomp;                        // [1024] (key << 32) | ~index: descending sort = reference order
+        det_radix_select(a.score, n, a.K, det_hist, cand);
         int P2 = 2;                                               // sort size: the power of two >= K (K = 10: 16 elements, 10 exchange steps)
         while (P2 < a.K) P2 <<= 1;
         for (int i = a.K + tid; i < P2; i += DET_THREADS) cand[i] = 0ull;                // padding sorts last
@@ -461,64 +461,62 @@ __global__ __launch_bounds__(DET_THREADS) void detect_kernel(const DetArgs a0) {
         if (tid < a.K) a.topk[tid] = (long long)(~(unsigned)(cand[tid] & 0xffffffffull));
         __syncthreads();
     } else {
-        // the retire-and-rescan rounds go through a working copy of the scores: in LDS when the map fits (<= 128 x 128, the 512 x 512
-        // input: a round's store -> 64 reloads of the winner's bucket is an LDS round trip instead of an L2 one), else in global scratch
+        // The retire-and-rescan rounds rank by the SAME (key << 32 | ~index) composites as the two paths above, so the order is theirs on
+        // every input: larger score first, lower index on ties, -0 == +0, NaN below every number and the lower index first among NaN.
+        // The working copy holds det_key + 1 per score (NaN = 1, +inf = 0xff800001: no overflow) and 0 for a retired one, which no
+        // score can equal: a genuine -inf is emitted once and a retired element never again (composite 0 = nothing, below everything).
+        // The copy lives in LDS when the map fits (<= 128 x 128, the 512 x 512 input: a round's store -> 64 reloads of the winner's
+        // bucket is an LDS round trip instead of an L2 one), else in global scratch.
         constexpr int WORK_LDS = 16384;
-        __shared__ float work_lds[WORK_LDS];
-        float* const work = n <= WORK_LDS ? work_lds : a.work;
-        for (int i = tid; i < n; i += DET_THREADS) work[i] = a.score[i];
+        __shared__ unsigned work_lds[WORK_LDS];
+        __shared__ unsigned long long red_c[DET_THREADS / 64];
+        unsigned* const work = n <= WORK_LDS ? work_lds : a.work;
+        for (int i = tid; i < n; i += DET_THREADS) work[i] = det_key(a.score[i]) + 1u;
         __syncthreads();
-        // K rounds of arg-max over a two-level structure: LDS holds the (max, arg-max) of every bucket of 64 consecutive scores;
+        // K rounds of maximum over a two-level structure: LDS holds the largest composite of every bucket of 64 consecutive scores;
         // a round reduces the bucket maxima (LDS only) and one wave re-scans the winner's bucket (64 loads in flight at once),
         // instead of every thread re-reading its share of the whole map from global memory: ~4 us per round instead of 24.
-        // Same order as a full scan: larger value first, lower index on ties, NaN never beats a number.
+        // K <= n (checked at the ABI) and a round retires exactly one live score, so a round's maximum is never 0.
         const int nb = (n + BK - 1) / BK;
         const int lane = tid & 63, wv = tid >> 6;
         const bool two_level = nb <= NB_MAX;
-        auto scan_bucket = [&](int b) {                              // one wave: arg-max of bucket b -> LDS
+        auto comp_of = [&](int i) {
+            const unsigned w = work[i];
+            return w ? ((unsigned long long)w << 32) | (unsigned)(~(unsigned)i) : 0ull;
+        };
+        auto scan_bucket = [&](int b) {                              // one wave: the largest composite of bucket b -> LDS
             const int i = b * BK + lane;
-            float v = i < n ? work[i] : -INFINITY; int vi = i < n ? i : 0x7fffffff;
+            unsigned long long c = i < n ? comp_of(i) : 0ull;
 #pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const float v2 = __shfl_down(v, off); const int i2 = __shfl_down(vi, off);
-                if (i2 != 0x7fffffff && (vi == 0x7fffffff || v2 > v || (v2 == v && i2 < vi))) { v = v2; vi = i2; }
-            }
-            if (lane == 0) { bmax[b] = v; bidx[b] = vi; }
+            for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(c, off); c = o > c ? o : c; }
+            if (lane == 0) bcomp[b] = c;
         };
         if (two_level) {
             for (int b = wv; b < nb; b += DET_THREADS / 64) scan_bucket(b);
             __syncthreads();
         }
-        float bv = -INFINITY; int bi = 0x7fffffff;
+        unsigned long long mine = 0ull;
         auto rescan = [&]() {                                        // fallback for huge maps: per-thread cached candidate
-            bv = -INFINITY; bi = 0x7fffffff;
-            for (int i = tid; i < n; i += DET_THREADS) {
-                const float v = work[i];
-                if (v > bv || bi == 0x7fffffff) { bv = v; bi = i; }
-            }
+            mine = 0ull;
+            for (int i = tid; i < n; i += DET_THREADS) { const unsigned long long c = comp_of(i); mine = c > mine ? c : mine; }
         };
         if (!two_level) rescan();
         for (int k = 0; k < a.K; ++k) {
-            float v; int idx;
+            unsigned long long c = mine;
             if (two_level) {
-                float cv = -INFINITY; int ci = 0x7fffffff;
-                for (int b = tid; b < nb; b += DET_THREADS) {
-                    const float v2 = bmax[b]; const int i2 = bidx[b];
-                    if (i2 != 0x7fffffff && (ci == 0x7fffffff || v2 > cv || (v2 == cv && i2 < ci))) { cv = v2; ci = i2; }
-                }
-                block_argmax_cached(cv, ci, red_v, red_i, v, idx);
+                for (int b = tid; b < nb; b += DET_THREADS) { const unsigned long long o = bcomp[b]; c = o > c ? o : c; }
+            }
+            const int idx = (int)(~(unsigned)(block_max_comp(c, red_c) & 0xffffffffull));
+            if (two_level) {
                 if (wv == 0) {                                       // wave 0 retires the winner and refreshes its bucket
-                    if (lane == 0) work[idx] = -INFINITY;
+                    if (lane == 0) work[idx] = 0u;
                     __builtin_amdgcn_wave_barrier();
                     __threadfence_block();
                     scan_bucket(idx / BK);
                 }
-            } else {
-                block_argmax_cached(bv, bi, red_v, red_i, v, idx);
-                if ((idx & (DET_THREADS - 1)) == tid) { work[idx] = -INFINITY; rescan(); }
-            }
+            } else if ((idx & (DET_THREADS - 1)) == tid) { work[idx] = 0u; rescan(); }
             if (tid == 0) a.topk[k] = idx;
-            __syncthreads();
+            __syncthreads();                                         // bcomp / red_c: this round's reads before the next one's writes
         }
     }
     __threadfence_block();
@@ -554,7 +552,7 @@ static int detect_launch(const float* score, const float* loc, const float* lm_h
     a.rows = rows; a.cols = cols; a.K = K; a.dc = det_cols; a.thresh = nms_thresh;
     a.dets = dets; a.topk = (long long*)topk_idx; a.keep = keep;
     char* s = (char*)scratch;
-    a.work = (float*)s; s += (size_t)rows * cols * 4;
+    a.work = (unsigned*)s; s += (size_t)rows * cols * 4;
     a.order = (int*)s; s += (size_t)K * 4;
     a.supp = (unsigned char*)s; s += ((size_t)K + 255) / 256 * 256;
     s = (char*)(((size_t)s + 7) & ~(size_t)7);                          // (inside the 256 spare bytes)

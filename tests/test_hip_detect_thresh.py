@@ -88,15 +88,11 @@ def _ref(m, mode, t, cap, nms=0.4):
 
 
 def _old_kernel(maps, b, mode, K, nms=0.4):
-    """the existing top-K kernel on image b's maps: rows, indices, keep list.  For K > 1024 (its arg-max rounds) the NaN scores are
-    handed to it as -inf: the rounds let a NaN that leads a bucket of 64 scores win the bucket, while the select paths (K <= 1024)
-    rank NaN below every number as documented.  -inf in the place of NaN leaves the K best numbers and their order as they are
-    (K never reaches down to -inf here), so the comparison still covers the threshold kernel's own NaN handling."""
+    """the existing top-K kernel on image b's maps, NaN scores included: rows, indices, keep list.  Every path of its selection, the
+    arg-max rounds of K > 1024 too, ranks NaN below every number (tests/test_hip_topk_paths.py), as the threshold kernel does by never
+    admitting NaN."""
     sl = lambda k: maps[k][b:b + 1]          # noqa: E731
     score = sl('score')
-    if K > 1024:
-        score = torch.where(torch.isnan(score), torch.full_like(score, float('-inf')), score)
-        assert int((score > float('-inf')).sum()) >= K
     d, tk, kp = DC._run_batch(score, sl('loc'), K, lm_heat=sl('lm_heat') if mode != 'box' else None,
                               lm_loc=sl('lm_loc') if mode == 'll' else None, nms_thresh=nms)
     kp = kp.cpu().numpy()[0]
