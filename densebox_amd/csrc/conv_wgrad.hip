@@ -2128,6 +2128,9 @@ static int wgrad_t(const dbx_view* dz, const dbx_view* x, int kh, int kw, int cp
                         ((size_t)dy->ptr % 16) == 0 && (dy->ld * ES) % 16 == 0 && (dy->c_off * ES) % 16 == 0 && ((size_t)pz->idx % 4) == 0 && dz->c_off % 8 == 0 &&
                         pz->ctot % 8 == 0 && dz->c_off + dz->c <= pz->ctot,
                     "wgrad pool dz: dy is the pooled map of dz (even extent, same channels / channel offset), 16-byte aligned, idx 4-byte aligned");
+        // every lane of a 64-channel co tile loads its 16 bytes of dy and its nibbles, masked or not: whole tiles only, inside the pixel
+        DBX_REQUIRE(dz->c % 64 == 0 && co == dz->c && dz->c_off + dz->c <= dz->ld && dy->c_off + dy->c <= dy->ld,
+                    "wgrad pool dz: needs co == dz->c, a multiple of 64 channels, and the channel range inside ld (dz->c %d, co %d)", dz->c, co);
         a.pdy = (const char*)dy->ptr + (size_t)dy->c_off * ES; a.pidx = pz->idx;
         a.p_hp = dy->h + 2 * dy->pad; a.p_wp = dy->w + 2 * dy->pad; a.p_ld = dy->ld; a.p_pad = dy->pad; a.p_h = dy->h; a.p_w = dy->w;
         a.z_h = dz->h; a.z_w = dz->w; a.z_pad = dz->pad; a.z_ctot = pz->ctot; a.z_coff = dz->c_off;
@@ -2274,6 +2277,7 @@ static int wgrad_pool_dz_t(const dbx_view* dy, const void* idx, int idx_ctot, co
 }
 extern "C" int dbx_conv_wgrad_pool_dz_ok(int32_t dtype, const dbx_view* dz, const dbx_view* x, int32_t kh, int32_t kw) {
     if (!dz || !x || (dtype != DBX_F16 && dtype != DBX_BF16) || dz->h % 2 || dz->w % 2) return 0;
+    if (dz->c % 64 != 0 || dz->c_off < 0 || dz->c_off + dz->c > dz->ld) return 0;     // whole 64-channel co tiles inside the pixel (co == dz->c is the call's to check)
     const WgradPlan p = wgrad_plan(dtype, dz, x, kh, kw);
     return (p.alltaps && p.strip && !p.wide2 && !p.all9 && !p.c8) ? 1 : 0;
 }

@@ -238,7 +238,8 @@ int dbx_head2_backward_up(int32_t dtype, const dbx_view* d_out, const dbx_view* 
  * (dbx_maxpool2x2_idx layout, idx_channels channels per pooled pixel); dz: the shape of the un-pooled gradient on its frame (congruent with
  * x; ptr is not read -- unless write_dz != 0: then the kernel ALSO writes the un-pooled gradient map there, every pixel of the frame incl. its
  * zero halo, bit for bit dbx_maxpool2x2_bwd_idx's, for a consumer that still wants it in memory: the pooling backward's own launch goes
- * away).  Exists where dbx_conv_wgrad_pool_dz_ok() returns 1 (16-bit, even H / W, the 3x3 column-strip kernel's shapes);
+ * away).  Exists where dbx_conv_wgrad_pool_dz_ok() returns 1 (16-bit, even H / W, the 3x3 column-strip kernel's shapes, dz->c a
+ * multiple of 64 inside its ld) and co == dz->c -- the kernel loads dy and the nibbles in whole 64-channel tiles; anything else is refused;
  * scratch as dbx_conv_wgrad_scratch_bytes(dz, x). */
 int dbx_conv_wgrad_pool_dz_ok(int32_t dtype, const dbx_view* dz, const dbx_view* x, int32_t kh, int32_t kw);
 int dbx_conv_wgrad_pool_dz(int32_t dtype, const dbx_view* dy, const void* idx, int32_t idx_channels, const dbx_view* dz, const dbx_view* x,
