@@ -35,16 +35,18 @@ def pack(L, dt, w, cin_pad, cout_pad, mode=0):
     return out
 
 
-CONV_CASES = [  # n, h, w, cin, cout, k, pad
-    (2, 20, 28, 64, 64, 3, 1), (3, 17, 23, 128, 256, 3, 1), (1, 30, 30, 512, 512, 3, 1), (2, 15, 15, 768, 1024, 1, 0),
-    (2, 14, 14, 64, 64, 5, 0), (1, 33, 9, 256, 128, 3, 1),
-    (10, 53, 100, 64, 64, 3, 1),      # ragged 8x32 tiles of the weights-stationary 64->64 kernel
-    (10, 240, 240, 64, 128, 3, 1),    # >= 1024 tiles of 512 pixels: conv3x3_band_kernel<512,128> (conv2_1 at batch 64)
-    (10, 240, 240, 128, 64, 3, 1),    # ... and <512,64> (conv2_1's data gradient)
-    (1, 64, 64, 512, 512, 3, 1),      # single-image maps: 192-pixel tiles, one workgroup per CU, 5-deep ring (conv4 of a 512 x 512 image)
-    (1, 128, 128, 256, 256, 3, 1),    # ... 192 x 128 tiles, 4-deep ring (conv3)
-    (1, 64, 60, 256, 512, 3, 1),
-    (1, 256, 256, 64, 128, 3, 1),     # 261 tiles of 256 pixels -> 232 of 288 (conv2_1 of a 512 x 512 image)
+CONV_CASES = [  # n, h, w, cin, cout, k, pad; the kernel names are what dbx_conv_plan reports at 256 CUs (tests/test_hip_conv_paths.py asserts them)
+    (2, 20, 28, 64, 64, 3, 1), (3, 17, 23, 128, 256, 3, 1), (1, 30, 30, 512, 512, 3, 1),      # conv3x3_band_kernel<128,64>
+    (2, 15, 15, 768, 1024, 1, 0),     # conv_igemm_dma_kernel<256,256>
+    (2, 14, 14, 64, 64, 5, 0),        # conv_igemm_dma_kernel<256,64>
+    (1, 33, 9, 256, 128, 3, 1),       # conv3x3_band_kernel<256,128>
+    (10, 53, 100, 64, 64, 3, 1),      # ragged 8x32 tiles of the weights-stationary 64->64 kernel: conv3x3_c64p_kernel<256,64>
+    (10, 240, 240, 64, 128, 3, 1),    # conv2_1 at batch 64: conv3x3_c64p_kernel<256,64>, one 64-cout slice per workgroup (conv3x3_band_kernel<512,128> under DBX_C64P_WIDE=0)
+    (10, 240, 240, 128, 64, 3, 1),    # >= 1024 tiles of 512 pixels: conv3x3_band_kernel<512,64> (conv2_1's data gradient)
+    (1, 64, 64, 512, 512, 3, 1),      # single-image maps: conv3x3_band_kernel<144,64>, one workgroup per CU, 5-deep ring (conv4 of a 512 x 512 image; <192,64> under DBX_BAND144=0)
+    (1, 128, 128, 256, 256, 3, 1),    # ... conv3x3_band_kernel<144,128>, 4-deep ring (conv3; <192,128> under DBX_BAND144=0)
+    (1, 64, 60, 256, 512, 3, 1),      # conv3x3_band_kernel<144,64>
+    (1, 256, 256, 64, 128, 3, 1),     # 261 tiles of 256 pixels -> 232 of 288: conv3x3_band_kernel<288,128> (conv2_1 of a 512 x 512 image)
 ]
 
 
