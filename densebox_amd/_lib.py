@@ -58,6 +58,10 @@ class CropFrame(C.Structure):
     _fields_ = [('src', C.c_void_p), ('sh', C.c_int32), ('sw', C.c_int32)]
 
 
+class EvalRecord(C.Structure):
+    _fields_ = [('score', C.c_double), ('lm_err', C.c_double), ('status', C.c_int32), ('frame', C.c_int32)]
+
+
 class ResizeJob(C.Structure):
     _fields_ = [('src', C.c_void_p), ('sh', C.c_int32), ('sw', C.c_int32), ('cx0', C.c_int32), ('cy0', C.c_int32),
                 ('cw', C.c_int32), ('ch', C.c_int32), ('pad_l', C.c_int32), ('pad_t', C.c_int32), ('pad_r', C.c_int32),
@@ -116,6 +120,8 @@ SIGNATURES = {
     'dbx_warp_batch_workspace_bytes': (_I64, [_I32]),
     'dbx_warp_perspective_batch_u8': (C.c_int, [C.POINTER(WarpJob), _I32, _I32, _VP, _VP, _VP]),
     'dbx_plate_crops_batch': (C.c_int, [_VP, _I32, _I32, _VP, _I64, _I64, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
+    'dbx_match_gt_batch': (C.c_int, [_VP, _I32, _I64, _VP, _VP, _I32, _I32, _VP, _I32, _VP, _VP, _I32, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
+    'dbx_eval_append': (C.c_int, [_VP, _I32, _I64, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     'dbx_resize_batch_workspace_bytes': (_I64, [_I32]),
     'dbx_resize_cubic_batch_u8': (C.c_int, [C.POINTER(ResizeJob), _I32, _I32, _VP, _VP, _VP]),
     'dbx_conv_wgrad_scratch_bytes': (_I64, [_I32, _PV, _PV, _I32, _I32]),

@@ -249,9 +249,10 @@ def detect_batch(net, images, K=10, nms_thresh=0.4, max_batch=32):
     return _detect_many('detect_batch', images, max_batch, lambda x: _detect_chunk(net, x, K, nms_thresh))
 
 
-def _detect_many(fn, images, max_batch, chunk):
+def _detect_many(fn, images, max_batch, chunk, with_index=False):
     """detect_batch's walk over a batch tensor or a list of single images: chunk(x) -> list of per-image results for every chunk of at
-    most max_batch same-shape images, results in input order.  Every check runs before the first chunk."""
+    most max_batch same-shape images, results in input order.  Every check runs before the first chunk.  with_index: chunk(x, idx) also
+    gets the input positions of the chunk's images (evaluate_batch finds their ground truth by them)."""
     if max_batch < 1:
         raise RuntimeError('%s: max_batch=%d must be positive' % (fn, max_batch))
     if not isinstance(images, (list, tuple)):
@@ -260,7 +261,8 @@ def _detect_many(fn, images, max_batch, chunk):
             raise RuntimeError('%s: empty batch' % fn)
         out = []
         for i in range(0, x.size(0), max_batch):
-            out += chunk(x[i:i + max_batch])
+            part = x[i:i + max_batch]
+            out += chunk(part, list(range(i, i + part.size(0)))) if with_index else chunk(part)
         return out
     if len(images) == 0:
         raise RuntimeError('%s: empty list of images' % fn)
@@ -281,7 +283,8 @@ def _detect_many(fn, images, max_batch, chunk):
         for c in range(0, len(idx), max_batch):
             part = idx[c:c + max_batch]
             dev = next((one[i].device for i in part if one[i].is_cuda), torch.device('cuda'))
-            res = chunk(torch.cat([one[i].to(dev) for i in part]))
+            x = torch.cat([one[i].to(dev) for i in part])
+            res = chunk(x, part) if with_index else chunk(x)
             for i, r in zip(part, res):
                 out[i] = r
     return out

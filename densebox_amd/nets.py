@@ -148,6 +148,15 @@ class _DenseBoxBase(nn.Module):
         from .decode import detect_plate_crops
         return detect_plate_crops(self, images, size=size, K=K, nms_thresh=nms_thresh, max_batch=max_batch)
 
+    def evaluate_batch(self, images, gt_boxes, *, evaluator, K=10, score_thresh=None, max_dets=1024, nms_thresh=0.4, max_batch=32,
+                       gt_ignore=None, gt_quads=None):
+        """forward -> decode + NMS -> match against ground truth -> append to `evaluator` (an evaluate.Evaluator), all on the device
+        and, in eval mode, in one hipGraph per chunk; nothing comes back to the host until evaluator.summary()
+        (densebox_amd.evaluate.evaluate_batch)."""
+        from .evaluate import evaluate_batch
+        return evaluate_batch(self, images, gt_boxes, evaluator=evaluator, K=K, score_thresh=score_thresh, max_dets=max_dets,
+                              nms_thresh=nms_thresh, max_batch=max_batch, gt_ignore=gt_ignore, gt_quads=gt_quads)
+
     def detect_batch_resized(self, images, size=720, K=10, nms_thresh=0.4, max_batch=32, score_thresh=None, max_dets=1024):
         """detect_batch() on uint8 frames of any sizes, each padded to a square and resized to size x size in one launch; a list of
         (dets, keep) in input order, coordinates mapped back to the source frames (densebox_amd.decode.detect_batch_resized)."""

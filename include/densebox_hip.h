@@ -58,7 +58,9 @@ const char* dbx_last_error(void);
  *      stay on the device)
  *      also at 13, without a bump: dbx_crop_frame, dbx_plate_crops_batch (fixed-size plate crops rectified on the device).  A pure
  *      addition changes no layout, argument list or scratch contract, so a binding written against 13 stays valid; a binding that needs
- *      the new entry point looks the symbol up */
+ *      the new entry point looks the symbol up
+ *      also at 13, without a bump: dbx_eval_record, dbx_match_gt_batch, dbx_eval_append (detections matched to ground truth and the
+ *      records of an evaluation pass accumulated on the device), pure additions likewise */
 #define DBX_ABI_VERSION 13
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
@@ -607,6 +609,60 @@ typedef struct dbx_crop_frame {
 int dbx_plate_crops_batch(const dbx_crop_frame* frames, int32_t nframes, int32_t c, const double* quads, int64_t row_stride,
                           int64_t frame_stride, const int32_t* sel, int32_t slots, int32_t ow, int32_t oh, uint8_t* dst, int32_t* ok,
                           double* m9_out, void* stream);
+
+/* ---- evaluation behind decode + NMS (no reference counterpart: its test* drivers only draw; the matching is the PASCAL VOC devkit's
+ * with the +1-pixel IoU of the reference's NMS, DenseBox.py:3398-3443) ----
+ * dbx_match_gt_batch: one launch, a workgroup per frame; it copies nothing from the host and never synchronises, so it can be captured
+ * into a hipGraph behind the decode.  Rows and lists are read where the decode left them:
+ *   prefix == NULL  dbx_detect_batch's slot layout: frame b's rows start at row b * slots of dets, its keep list is the slots + 1 words
+ *                   at keep + b * (slots + 1); det_rows >= batch * slots.
+ *   prefix != NULL  dbx_detect_thresh_batch's packed layout with slots = its max_dets: prefix is the device int32 [batch + 1] that call
+ *                   leaves at counts + 2 * batch; frame b's n_b = P[b + 1] - P[b] rows start at row P[b], its list is at word P[b] + b of
+ *                   keep (the address the decode wrote its lists to; det_rows + batch words).
+ *   det_rows        the capacity of dets in rows of det_cols (5 or 13) float64.
+ * The detections of a frame are its kept rows in list order, numbered i = 0..k-1 by position.  gt: float64 [batch][max_gt][gt_cols],
+ * a box (x1, y1, x2, y2) in the rows' coordinates and, with gt_cols == 12, a quad of 8 values in the order of row columns 5..12;
+ * gt_counts int32 [batch], clamped to 0..max_gt; gt_ignore uint8 [batch][max_gt] or NULL (no box is ignored).
+ * IoU in float64, the NMS's formula: areas (x2 - x1 + 1) * (y2 - y1 + 1), intersection sides max(0, min(x2) - max(x1) + 1), ovr = inter /
+ * (area_d + area_g - inter), the product rounded before the subtraction.  For detection i: jmax = the GT of the largest ovr (the lowest
+ * index on ties; a NaN ovr never wins), ovmax = that ovr (-inf without one); matched when ovmax > iou_thresh, strictly.  status 0 (FP) and
+ * gt_index -1 when not matched; status -1 (ignored) and gt_index jmax when jmax carries the ignore flag; status 1 (TP) when i is the
+ * first detection in list order matched to jmax, else status 0 (duplicate FP), both with gt_index jmax.  Outputs (device), in slot
+ * layout by list position:
+ *   status, gt_index  int32 [batch][slots]: EVERY word is written; positions past the list count get status -2 and gt_index -1.
+ *   iou               float64 [batch][slots]: ovmax, positions below the count only.
+ *   lm_err            float64 [batch][slots] or NULL; a pointer needs det_cols == 13 && gt_cols == 12.  For a TP the mean over the four
+ *                     corners of the distance between the row's landmark and the GT's, over sqrt of the GT box's area; NaN otherwise;
+ *                     positions below the count only.
+ *   tally             int32 [batch][5]: (counted positions, TP, FP, ignored, GT boxes without the ignore flag), every word written.
+ * Whatever the device data says, nothing outside the buffers is read: a keep count is clamped to 0..min(slots, n_b); a frame whose
+ * prefix pair is negative, decreasing or ends beyond det_rows is empty; a keep entry outside 0..n_b-1 gives its position status -2
+ * (iou and lm_err NaN) and the position is not counted.  GT boxes and the per-GT claim words live in LDS (45 bytes per GT); there is no
+ * scratch buffer.  Refused with DBX_ERR_ARG before anything is queued: batch < 0, det_cols other than 5 or 13, gt_cols other than 4 or
+ * 12, slots outside 1..4096, max_gt outside 1..1024, det_rows < 0 or (slot layout) below batch * slots, a NaN iou_thresh, lm_err with
+ * other columns than 13 / 12, a null pointer (prefix, gt_ignore and lm_err excepted).  batch == 0: no-op.
+ *
+ * dbx_eval_append: one small launch behind the match, capturable likewise.  Every counted position of the call becomes a record, in
+ * frame order, then list order, at records[cursor...]; the running totals are updated; the result does not depend on scheduling.
+ * The dets / keep / prefix / slots description is the match's; status, lm_err (may be NULL: the records hold NaN) and tally are what the
+ * match wrote.  state: device int64 [8] = {cursor, dropped, frames, n_gt, tp, fp, ignored, reserved}, zero before the first call.
+ * record.frame = the running frame number, state.frames + b.  Records past `capacity` are not written and are counted in dropped; the
+ * totals take the whole tallies.  Refused: the match's refusals of the shared arguments, capacity < 0, a null pointer (prefix and lm_err
+ * excepted; records only when capacity is 0).  batch == 0: no-op.
+ * The record is 24 bytes: score at 0, lm_err at 8, status at 16, frame at 20. */
+typedef struct dbx_eval_record {
+    double  score;     /* column 4 of the row */
+    double  lm_err;    /* NaN unless a TP matched with landmarks */
+    int32_t status;    /* 1 TP, 0 FP, -1 ignored */
+    int32_t frame;     /* running frame number of the evaluation pass */
+} dbx_eval_record;
+int dbx_match_gt_batch(const double* dets, int32_t det_cols, int64_t det_rows, const int32_t* keep, const int32_t* prefix,
+                       int32_t batch, int32_t slots, const double* gt, int32_t gt_cols, const int32_t* gt_counts,
+                       const uint8_t* gt_ignore, int32_t max_gt, double iou_thresh, int32_t* status, int32_t* gt_index,
+                       double* iou, double* lm_err, int32_t* tally, void* stream);
+int dbx_eval_append(const double* dets, int32_t det_cols, int64_t det_rows, const int32_t* keep, const int32_t* prefix,
+                    int32_t batch, int32_t slots, const int32_t* status, const double* lm_err, const int32_t* tally,
+                    dbx_eval_record* records, int64_t capacity, int64_t* state, void* stream);
 
 /* ---- batched pad + bicubic resize (pad_img + cv2.resize(..., INTER_CUBIC), DenseBox.py:1282-1340; the patch cutters' resize of a
  * cropped window) ----
