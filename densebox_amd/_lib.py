@@ -62,6 +62,15 @@ class EvalRecord(C.Structure):
     _fields_ = [('score', C.c_double), ('lm_err', C.c_double), ('status', C.c_int32), ('frame', C.c_int32)]
 
 
+class Track(C.Structure):
+    _fields_ = [('box', C.c_double * 4), ('vel', C.c_double * 4), ('score', C.c_double), ('best_score', C.c_double), ('id', C.c_int32),
+                ('hits', C.c_int32), ('age', C.c_int32), ('first_frame', C.c_int32), ('last_frame', C.c_int32), ('best_frame', C.c_int32)]
+
+
+class TrackRecord(C.Structure):
+    _fields_ = [('stream', C.c_int32), ('reserved', C.c_int32), ('t', Track)]
+
+
 class ResizeJob(C.Structure):
     _fields_ = [('src', C.c_void_p), ('sh', C.c_int32), ('sw', C.c_int32), ('cx0', C.c_int32), ('cy0', C.c_int32),
                 ('cw', C.c_int32), ('ch', C.c_int32), ('pad_l', C.c_int32), ('pad_t', C.c_int32), ('pad_r', C.c_int32),
@@ -122,6 +131,9 @@ SIGNATURES = {
     'dbx_plate_crops_batch': (C.c_int, [_VP, _I32, _I32, _VP, _I64, _I64, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
     'dbx_match_gt_batch': (C.c_int, [_VP, _I32, _I64, _VP, _VP, _I32, _I32, _VP, _I32, _VP, _VP, _I32, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
     'dbx_eval_append': (C.c_int, [_VP, _I32, _I64, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
+    'dbx_track_update_batch': (C.c_int, [_VP, _I32, _I64, _VP, _VP, _I32, _I32, _VP, _VP, _I32, _I32, _I32, _D, _I32, _D, _D, _D, _VP, _VP, _VP,
+                                         _VP, _VP, _VP]),
+    'dbx_track_append': (C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP, _I64, _VP, _VP]),
     'dbx_resize_batch_workspace_bytes': (_I64, [_I32]),
     'dbx_resize_cubic_batch_u8': (C.c_int, [C.POINTER(ResizeJob), _I32, _I32, _VP, _VP, _VP]),
     'dbx_conv_wgrad_scratch_bytes': (_I64, [_I32, _PV, _PV, _I32, _I32]),

@@ -157,6 +157,14 @@ class _DenseBoxBase(nn.Module):
         return evaluate_batch(self, images, gt_boxes, evaluator=evaluator, K=K, score_thresh=score_thresh, max_dets=max_dets,
                               nms_thresh=nms_thresh, max_batch=max_batch, gt_ignore=gt_ignore, gt_quads=gt_quads)
 
+    def track_batch(self, images, *, tracker, stream0=0, K=10, score_thresh=None, max_dets=1024, nms_thresh=0.4, max_batch=32):
+        """forward -> decode + NMS -> association with the tracks of camera streams stream0.. in `tracker` (a track.Tracker), all on
+        the device and, in eval mode, in one hipGraph per chunk: a list of (dets, keep, track_id, track_hits) in input order
+        (densebox_amd.track.track_batch)."""
+        from .track import track_batch
+        return track_batch(self, images, tracker=tracker, stream0=stream0, K=K, score_thresh=score_thresh, max_dets=max_dets,
+                           nms_thresh=nms_thresh, max_batch=max_batch)
+
     def detect_batch_resized(self, images, size=720, K=10, nms_thresh=0.4, max_batch=32, score_thresh=None, max_dets=1024):
         """detect_batch() on uint8 frames of any sizes, each padded to a square and resized to size x size in one launch; a list of
         (dets, keep) in input order, coordinates mapped back to the source frames (densebox_amd.decode.detect_batch_resized)."""

@@ -60,7 +60,9 @@ const char* dbx_last_error(void);
  *      addition changes no layout, argument list or scratch contract, so a binding written against 13 stays valid; a binding that needs
  *      the new entry point looks the symbol up
  *      also at 13, without a bump: dbx_eval_record, dbx_match_gt_batch, dbx_eval_append (detections matched to ground truth and the
- *      records of an evaluation pass accumulated on the device), pure additions likewise */
+ *      records of an evaluation pass accumulated on the device), pure additions likewise
+ *      also at 13, without a bump: dbx_track, dbx_track_record, dbx_track_update_batch, dbx_track_append (multi-stream tracking by
+ *      detection with its state on the device), pure additions likewise */
 #define DBX_ABI_VERSION 13
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
@@ -663,6 +665,76 @@ int dbx_match_gt_batch(const double* dets, int32_t det_cols, int64_t det_rows, c
 int dbx_eval_append(const double* dets, int32_t det_cols, int64_t det_rows, const int32_t* keep, const int32_t* prefix,
                     int32_t batch, int32_t slots, const int32_t* status, const double* lm_err, const int32_t* tally,
                     dbx_eval_record* records, int64_t capacity, int64_t* state, void* stream);
+
+/* ---- multi-stream tracking behind decode + NMS (no reference counterpart: tracking by detection with an alpha-beta filter per box
+ * coordinate and greedy IoU association, the +1-pixel IoU of the reference's NMS, DenseBox.py:3398-3443) ----
+ * dbx_track_update_batch: one launch, a workgroup per frame; it copies nothing from the host and never synchronises, so it can be captured
+ * into a hipGraph behind the decode.  Frame b of the launch belongs to stream stream0 + b, so a launch never holds two frames of one
+ * stream.  dets / det_cols / det_rows / keep / prefix / batch / slots describe the rows and keep lists exactly as for dbx_match_gt_batch
+ * (slot layout when prefix == NULL, dbx_detect_thresh_batch's packed layout otherwise), with slots in 1..1024.
+ * State (device): headers int32 [streams][4] = {frame, next_id, unborn, reserved} and tracks dbx_track [streams][max_tracks]; id < 0
+ * marks a free slot, whatever else it holds; all-zero headers with all ids -1 are the initial state.
+ * Stream s at its frame number f = header.frame; the detections are the kept rows in list order, i = 0..k-1:
+ *   A  predict   every live slot t: p_t = box_t + vel_t (four additions).
+ *   B  associate for i ascending, over the live slots not yet claimed in this frame: ovr(p_t, row_i) by the NMS's formula as
+ *                dbx_match_gt_batch states it (+1 sides, the product rounded before the subtraction); the winner is the slot of the
+ *                largest ovr, the lowest slot index on ties, a NaN ovr never wins; the slot is claimed by i when that ovr > iou_thresh,
+ *                strictly.  Slots born in D are never candidates in the same frame.
+ *   C  update    every live slot in ascending slot order.  Claimed by i: r = row_i.box - p; box = p + alpha * r; vel = vel + beta * r;
+ *                score = row_i[4]; if score > best_score (strictly): best_score = score, best_frame = f; hits += 1, age = 0,
+ *                last_frame = f.  Unclaimed: box = p, age += 1, and when age > max_age the slot is retired: its record is copied to
+ *                retired[b][n++] (ascending slot order) and its id in the table set to -1 (the rest of the slot keeps the record).
+ *   D  births    unmatched detections in list order.  Born when all four coordinates are finite, row[4] >= birth_score (a NaN score
+ *                fails) and a free slot exists; it takes the lowest free index, slots freed in C included; id = next_id++, box =
+ *                row.box, vel = 0, score = best_score = row[4], hits = 1, age = 0, first_frame = last_frame = best_frame = f.
+ *                Otherwise the detection gets no track and header.unborn += 1.
+ *   E            header.frame = f + 1.
+ * Outputs (device), slot layout by list position:
+ *   track_id    int32 [batch][slots]: EVERY word is written; the track's id, -1 for a counted position without a track, -2 for positions
+ *               past the count and for a keep entry outside 0..n_b-1, which is not counted.
+ *   track_slot  int32 [batch][slots]: EVERY word is written; the slot index, -1 wherever track_id < 0.
+ *   track_hits  int32 [batch][slots]: the track's hits after the update (0 wherever track_id < 0); positions below the count only.
+ *   retired     dbx_track [batch][max_tracks]: the first tally[b][4] records of each frame.
+ *   tally       int32 [batch][6]: (counted positions, matched, born, unborn, retired, live after), every word written.
+ * Whatever the device data says, nothing outside the buffers is read or written: a keep count is clamped to 0..min(slots, n_b); a frame
+ * whose prefix pair is negative, decreasing or ends beyond det_rows has no detections and its tracks coast.  One thread per track slot
+ * keeps the slot's record in registers; LDS holds 44 bytes per list position (box, score, the slot it ended up with) and 16 bytes per
+ * track slot (free-list entry, birth, id and hits for the outputs): 48 KB at the limits; there is no scratch buffer.
+ * Refused with DBX_ERR_ARG before anything is queued: batch < 0, stream0 < 0, stream0 + batch > streams, det_cols other than 5 or 13,
+ * slots outside 1..1024, max_tracks outside 1..256, max_age < 0, a NaN iou_thresh, alpha, beta or birth_score, det_rows < 0 or (slot
+ * layout) below batch * slots, a null pointer (prefix excepted).  batch == 0: no-op.
+ *
+ * dbx_track_append: one small launch behind the update, capturable likewise.  The retired records of the call go to records[cursor...]
+ * in frame order, then `retired` order, with stream = stream0 + b; the result does not depend on scheduling.  retired and tally are what
+ * the update wrote (tally[b][4] is clamped to 0..max_tracks).  state: device int64 [4] = {cursor, dropped, retired_total, reserved},
+ * zero before the first call.  Records past `capacity` are not written and are counted in dropped; retired_total counts them all.
+ * Refused: batch < 0, stream0 < 0, max_tracks outside 1..256, capacity < 0, a null pointer (records only when capacity is 0).
+ * batch == 0: no-op.
+ * dbx_track is 104 bytes (box at 0, vel at 32, score at 64, best_score at 72, the six int32 from 80); dbx_track_record is 112 bytes
+ * (stream at 0, reserved at 4, the track at 8). */
+typedef struct dbx_track {
+    double  box[4];        /* x1, y1, x2, y2 after the last update (the prediction while coasting) */
+    double  vel[4];        /* per-coordinate velocity, pixels per frame */
+    double  score;         /* column 4 of the last matched row */
+    double  best_score;    /* the largest score seen, and the frame it was seen in (best_frame) */
+    int32_t id;            /* >= 0 live, < 0 free */
+    int32_t hits;          /* detections matched to the track, its birth included */
+    int32_t age;           /* frames since the last match */
+    int32_t first_frame;
+    int32_t last_frame;    /* the frame of the last match */
+    int32_t best_frame;
+} dbx_track;
+typedef struct dbx_track_record {
+    int32_t   stream;
+    int32_t   reserved;
+    dbx_track t;
+} dbx_track_record;
+int dbx_track_update_batch(const double* dets, int32_t det_cols, int64_t det_rows, const int32_t* keep, const int32_t* prefix,
+                           int32_t batch, int32_t slots, int32_t* headers, dbx_track* tracks, int32_t streams, int32_t stream0,
+                           int32_t max_tracks, double iou_thresh, int32_t max_age, double alpha, double beta, double birth_score,
+                           int32_t* track_id, int32_t* track_slot, int32_t* track_hits, dbx_track* retired, int32_t* tally, void* stream);
+int dbx_track_append(const dbx_track* retired, const int32_t* tally, int32_t batch, int32_t max_tracks, int32_t stream0,
+                     dbx_track_record* records, int64_t capacity, int64_t* state, void* stream);
 
 /* ---- batched pad + bicubic resize (pad_img + cv2.resize(..., INTER_CUBIC), DenseBox.py:1282-1340; the patch cutters' resize of a
  * cropped window) ----
