@@ -71,6 +71,15 @@ class TrackRecord(C.Structure):
     _fields_ = [('stream', C.c_int32), ('reserved', C.c_int32), ('t', Track)]
 
 
+class Shot(C.Structure):
+    _fields_ = [('key', C.c_double), ('score', C.c_double), ('sharpness', C.c_int64), ('id', C.c_int32), ('frame', C.c_int32),
+                ('shots', C.c_int32), ('reserved', C.c_int32)]
+
+
+class ShotRecord(C.Structure):
+    _fields_ = [('stream', C.c_int32), ('slot', C.c_int32), ('shot', Shot)]
+
+
 class ResizeJob(C.Structure):
     _fields_ = [('src', C.c_void_p), ('sh', C.c_int32), ('sw', C.c_int32), ('cx0', C.c_int32), ('cy0', C.c_int32),
                 ('cw', C.c_int32), ('ch', C.c_int32), ('pad_l', C.c_int32), ('pad_t', C.c_int32), ('pad_r', C.c_int32),
@@ -134,6 +143,9 @@ SIGNATURES = {
     'dbx_track_update_batch': (C.c_int, [_VP, _I32, _I64, _VP, _VP, _I32, _I32, _VP, _VP, _I32, _I32, _I32, _D, _I32, _D, _D, _D, _VP, _VP, _VP,
                                          _VP, _VP, _VP]),
     'dbx_track_append': (C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP, _I64, _VP, _VP]),
+    'dbx_crop_sharpness': (C.c_int, [_VP, _I64, _I32, _I32, _I32, _VP, _VP]),
+    'dbx_track_gallery_update': (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32,
+                                           _I32, _I32, _I64, _I32, _D, _I32, _VP]),
     'dbx_resize_batch_workspace_bytes': (_I64, [_I32]),
     'dbx_resize_cubic_batch_u8': (C.c_int, [C.POINTER(ResizeJob), _I32, _I32, _VP, _VP, _VP]),
     'dbx_conv_wgrad_scratch_bytes': (_I64, [_I32, _PV, _PV, _I32, _I32]),

@@ -165,6 +165,14 @@ class _DenseBoxBase(nn.Module):
         return track_batch(self, images, tracker=tracker, stream0=stream0, K=K, score_thresh=score_thresh, max_dets=max_dets,
                            nms_thresh=nms_thresh, max_batch=max_batch)
 
+    def track_plate_crops(self, images, *, tracker, gallery, stream0=0, K=10, nms_thresh=0.4, max_batch=32):
+        """track_batch() on uint8 frames with the best plate crop of every track kept on the device in `gallery` (a
+        gallery.PlateGallery made for `tracker`), in eval mode in one hipGraph per chunk: a list of (dets, keep, track_id, track_hits) in
+        input order (densebox_amd.gallery.track_plate_crops)."""
+        from .gallery import track_plate_crops
+        return track_plate_crops(self, images, tracker=tracker, gallery=gallery, stream0=stream0, K=K, nms_thresh=nms_thresh,
+                                 max_batch=max_batch)
+
     def detect_batch_resized(self, images, size=720, K=10, nms_thresh=0.4, max_batch=32, score_thresh=None, max_dets=1024):
         """detect_batch() on uint8 frames of any sizes, each padded to a square and resized to size x size in one launch; a list of
         (dets, keep) in input order, coordinates mapped back to the source frames (densebox_amd.decode.detect_batch_resized)."""

@@ -62,7 +62,9 @@ const char* dbx_last_error(void);
  *      also at 13, without a bump: dbx_eval_record, dbx_match_gt_batch, dbx_eval_append (detections matched to ground truth and the
  *      records of an evaluation pass accumulated on the device), pure additions likewise
  *      also at 13, without a bump: dbx_track, dbx_track_record, dbx_track_update_batch, dbx_track_append (multi-stream tracking by
- *      detection with its state on the device), pure additions likewise */
+ *      detection with its state on the device), pure additions likewise
+ *      also at 13, without a bump: dbx_shot, dbx_shot_record, dbx_crop_sharpness, dbx_track_gallery_update (the best plate crop of
+ *      every track kept on the device), pure additions likewise */
 #define DBX_ABI_VERSION 13
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
@@ -735,6 +737,71 @@ int dbx_track_update_batch(const double* dets, int32_t det_cols, int64_t det_row
                            int32_t* track_id, int32_t* track_slot, int32_t* track_hits, dbx_track* retired, int32_t* tally, void* stream);
 int dbx_track_append(const dbx_track* retired, const int32_t* tally, int32_t batch, int32_t max_tracks, int32_t stream0,
                      dbx_track_record* records, int64_t capacity, int64_t* state, void* stream);
+
+/* ---- best-shot gallery behind the crops and the tracking update (no reference counterpart): per track the best plate crop the camera
+ * ever saw of it, kept on the device until the track ends ----
+ * dbx_crop_sharpness: out[i] = the focus measure of crop i of crops uint8 [n][oh][ow][c], one workgroup per crop.  c is 1 or 3; the
+ * luma is Y = 4 * v (c == 1) or Y = c0 + 2 * c1 + c2 (c == 3), the same for RGB and BGR, at most 1020; for every interior pixel
+ * L = 4 * Y(y, x) - Y(y-1, x) - Y(y+1, x) - Y(y, x-1) - Y(y, x+1), and out[i] is the sum of L * L over the interior in 64-bit integer
+ * arithmetic (0 when oh < 3 or ow < 3): exact, whatever the order of the reduction.  The luma plane is staged in LDS as 16-bit values,
+ * hence oh * ow <= 16384; the sum goes per thread, then by wave shuffle, then across the waves through LDS; there are no atomics.
+ * Refused with DBX_ERR_ARG before anything is queued: n < 0, c other than 1 or 3, oh or ow < 1, oh * ow > 16384, a null pointer.
+ * n == 0: no-op.
+ *
+ * dbx_track_gallery_update: one launch, a workgroup of 256 threads per (track slot t, frame b) on a grid of (max_tracks, batch); it
+ * copies nothing from the host and never synchronises, so it can be captured into a hipGraph.  It runs BEHIND dbx_track_update_batch and
+ * dbx_plate_crops_batch of the same frames and BEFORE dbx_track_append of the same call, so that it reads the append cursor as it stood
+ * before the call.  Inputs (device): tracks and headers as the update left them; track_slot int32 [batch][slots]; crops uint8
+ * [batch][slots][oh][ow][c] and ok int32 [batch][slots], both by list position, as dbx_plate_crops_batch writes them with sel = keep;
+ * retired dbx_track [batch][max_tracks] and tally int32 [batch][6] as the update wrote them; append_state, dbx_track_append's int64 [4],
+ * of which only word 0, the cursor, is read.  Gallery state (device): shots dbx_shot [streams][max_tracks]; shot_crops uint8
+ * [streams][max_tracks][oh][ow][c]; arena dbx_shot_record [capacity], every shot.id -1 initially; arena_crops uint8
+ * [capacity][oh][ow][c]; gstate int64 [4] = {ended, stored, lost, dropped}.  A free entry of shots has id = -1; a fresh entry for track
+ * id i has key = -inf, score = NaN, sharpness = 0, id = i, frame = -1, shots = 0, reserved = 0.
+ * For stream s = stream0 + b and slot t, with G = shots[s][t], K = tracks[s][t], f = headers[s].frame - 1 and R_b = tally[b][4] clamped
+ * to 0..max_tracks:
+ *   1  ended      G.id >= 0 and K.id != G.id: ended += 1.  n = the lowest index below R_b with retired[b][n].id == G.id.  Found: i =
+ *                 cursor + sum of R_b' over b' < b + n, the index dbx_track_append is about to give that record; when the cursor is
+ *                 not negative and i < capacity, arena[i] = {s, t, G}, arena_crops[i] = shot_crops[s][t] and stored += 1, otherwise
+ *                 dropped += 1.  Not found (the tracker was advanced without the gallery in between): lost += 1.  In every case
+ *                 G.id = -1.
+ *   2  adoption   K.id >= 0 and G.id != K.id: G becomes the fresh entry for K.id and shot_crops[s][t] is zeroed.  A slot retired and
+ *                 reborn in one frame passes through 1 and 2 in that order.
+ *   3  candidate  K.id >= 0 and a list position j has track_slot[b][j] == t (the lowest such j below slots).  The crop is a candidate
+ *                 when ok[b][j] != 0 and K.score >= min_score (a NaN score fails; K.score is the row's score, which the update stored
+ *                 for every track matched or born in this frame).  Then S = the sharpness of crops[b][j], key = (double)S under policy
+ *                 0 or K.score under policy 1, G.shots += 1, and when this is the first candidate (shots was 0) or key > G.key,
+ *                 strictly: G.key = key, G.score = K.score, G.sharpness = S, G.frame = f and shot_crops[s][t] = the crop (16-byte
+ *                 words where the addresses allow).  A live track without a list position coasts and is left alone.
+ * The counters are integer adds, one per counter and workgroup at most; nothing else depends on scheduling.  commit == 0: the launch
+ * does all its reads and the reduction and writes nothing (the warm-up runs of a graph capture).  Whatever the device data says,
+ * nothing outside the buffers is read or written: R_b is clamped, a track_slot entry outside 0..max_tracks-1 names no slot, a negative
+ * cursor is a drop.  LDS: the luma plane and 64 bytes; there is no scratch buffer.
+ * Refused with DBX_ERR_ARG before anything is queued: batch < 0, stream0 < 0, stream0 + batch > streams, slots outside 1..1024,
+ * max_tracks outside 1..256, c other than 1 or 3, oh or ow < 1, oh * ow > 16384, capacity < 0, policy other than 0 or 1, a NaN
+ * min_score, a null pointer (arena and arena_crops only when capacity is 0), batch above 65535 (one grid).  batch == 0: no-op.
+ * dbx_shot is 40 bytes (key at 0, score at 8, sharpness at 16, the four int32 from 24); dbx_shot_record is 48 bytes (stream at 0, slot
+ * at 4, the shot at 8). */
+typedef struct dbx_shot {
+    double  key;           /* what the shots are ranked by: (double)sharpness under policy 0, score under policy 1; -inf without a shot */
+    double  score;         /* the track's score in the frame of the shot; NaN without a shot */
+    int64_t sharpness;     /* dbx_crop_sharpness of the shot */
+    int32_t id;            /* the track's id; < 0 free */
+    int32_t frame;         /* the stream's frame number of the shot; -1 without a shot */
+    int32_t shots;         /* candidates seen */
+    int32_t reserved;
+} dbx_shot;
+typedef struct dbx_shot_record {
+    int32_t  stream;
+    int32_t  slot;
+    dbx_shot shot;
+} dbx_shot_record;
+int dbx_crop_sharpness(const uint8_t* crops, int64_t n, int32_t oh, int32_t ow, int32_t c, int64_t* out, void* stream);
+int dbx_track_gallery_update(const dbx_track* tracks, const int32_t* headers, const int32_t* track_slot, const uint8_t* crops,
+                             const int32_t* ok, const dbx_track* retired, const int32_t* tally, const int64_t* append_state,
+                             dbx_shot* shots, uint8_t* shot_crops, dbx_shot_record* arena, uint8_t* arena_crops, int64_t* gstate,
+                             int32_t batch, int32_t slots, int32_t streams, int32_t stream0, int32_t max_tracks, int32_t oh, int32_t ow,
+                             int32_t c, int64_t capacity, int32_t policy, double min_score, int32_t commit, void* stream);
 
 /* ---- batched pad + bicubic resize (pad_img + cv2.resize(..., INTER_CUBIC), DenseBox.py:1282-1340; the patch cutters' resize of a
  * cropped window) ----
