@@ -10,20 +10,48 @@ from . import _lib
 from ._lib import check, ptr, stream_ptr
 
 
-def _run(score_map, loc_map, M, N, K, lm_heat=None, lm_loc=None, nms_thresh=0.4):
-    rows, cols = M // 4, N // 4
-    assert score_map.size() == torch.Size([1, 1, rows, cols])
-    assert loc_map.size() == torch.Size([1, 4, rows, cols])
+def _integer(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+
+def _keep_list(k):
+    """the python list of kept rows in a keep buffer [count, idx...] on the host"""
+    return [int(v) for v in k[1:1 + int(k[0])]]
+
+
+def _det_cols(net):
+    return 5 if net.KIND == 'DenseBox' else 13
+
+
+def _require_landmarks(fn, net, to='rectify'):
+    if net.KIND == 'DenseBox':
+        raise RuntimeError('%s: DenseBox rows have no landmarks to %s; use DenseBoxLM or DenseBoxLMLOC' % (fn, to))
+
+
+def _decode_inputs(score, loc, lm_heat, lm_loc, batch=None):
+    """The prologue of every decode launcher: shape checks of the [B,C,rows,cols] maps (B == batch where one is given), the device (the
+    score map's, or the current CUDA device for host maps) and the fp32-contiguous maps on it.  Returns (score, loc, lm_heat, lm_loc, B,
+    rows, cols, row columns 5|13, device)."""
+    B, _, rows, cols = score.shape
+    assert (batch is None or B == batch) and score.size(1) == 1 and loc.size() == torch.Size([B, 4, rows, cols])
     if lm_heat is not None:
-        assert lm_heat.size() == torch.Size([1, 4, rows, cols])
+        assert lm_heat.size() == torch.Size([B, 4, rows, cols])
     if lm_loc is not None:
-        assert lm_loc.size() == torch.Size([1, 8, rows, cols])
-    dev = score_map.device if score_map.is_cuda else torch.device('cuda')
+        assert lm_loc.size() == torch.Size([B, 8, rows, cols])
+    dev = score.device if score.is_cuda else torch.device('cuda')
 
     def f(t):
         return None if t is None else t.detach().to(dev, torch.float32).contiguous()
-    s, l, hm, ll = f(score_map), f(loc_map), f(lm_heat), f(lm_loc)
-    dc = 5 if (hm is None and ll is None) else 13
+    return f(score), f(loc), f(lm_heat), f(lm_loc), B, rows, cols, 5 if (lm_heat is None and lm_loc is None) else 13, dev
+
+
+def _run(score_map, loc_map, M, N, K, lm_heat=None, lm_loc=None, nms_thresh=0.4):
+    s, l, hm, ll, _, rows, cols, dc, dev = _decode_inputs(score_map, loc_map, lm_heat, lm_loc, batch=1)
+    assert (rows, cols) == (M // 4, N // 4)
     dets = torch.empty((K, dc), dtype=torch.float64, device=dev)
     topk = torch.empty(K, dtype=torch.int64, device=dev)
     keep = torch.empty(K + 1, dtype=torch.int32, device=dev)
@@ -57,24 +85,12 @@ def NMS(dets, nms_thresh=0.4):
     keep = torch.empty(n + 1, dtype=torch.int32, device=d.device)
     scratch = torch.empty(5 * n + 16, dtype=torch.uint8, device=d.device)
     check(_lib.lib().dbx_nms(ptr(d), n, dc, float(nms_thresh), ptr(keep), ptr(scratch), stream_ptr()))
-    k = keep.cpu().numpy()
-    return [int(v) for v in k[1:1 + int(k[0])]]
+    return _keep_list(keep.cpu().numpy())
 
 
 def _run_batch(score_map, loc_map, K, lm_heat=None, lm_loc=None, nms_thresh=0.4):
     """dbx_detect_batch over [B,C,rows,cols] maps: dets [B,K,5|13] float64, topk [B,K] int64, keep [B,K+1] int32 (device)."""
-    B, _, rows, cols = score_map.shape
-    assert score_map.size(1) == 1 and loc_map.size() == torch.Size([B, 4, rows, cols])
-    if lm_heat is not None:
-        assert lm_heat.size() == torch.Size([B, 4, rows, cols])
-    if lm_loc is not None:
-        assert lm_loc.size() == torch.Size([B, 8, rows, cols])
-    dev = score_map.device if score_map.is_cuda else torch.device('cuda')
-
-    def f(t):
-        return None if t is None else t.detach().to(dev, torch.float32).contiguous()
-    s, l, hm, ll = f(score_map), f(loc_map), f(lm_heat), f(lm_loc)
-    dc = 5 if (hm is None and ll is None) else 13
+    s, l, hm, ll, B, rows, cols, dc, dev = _decode_inputs(score_map, loc_map, lm_heat, lm_loc)
     dets = torch.empty((B, K, dc), dtype=torch.float64, device=dev)
     topk = torch.empty((B, K), dtype=torch.int64, device=dev)
     keep = torch.empty((B, K + 1), dtype=torch.int32, device=dev)
@@ -98,38 +114,56 @@ def _maps(kind, outs):
     return outs[1], outs[2], outs[3], outs[4]
 
 
-def _detect_eager(net, image, K, nms_thresh):
-    M, N = image.size(2), image.size(3)
-    with torch.no_grad():
-        outs = net(image)
-    s, l, hm, ll = _maps(net.KIND, outs)
-    dets, _, keep = _run(s, l, M, N, K, lm_heat=hm, lm_loc=ll, nms_thresh=nms_thresh)
-    return dets, keep
-
-
-def _detect_batch_eager(net, images, K, nms_thresh):
+def _forward_maps(net, images):
     with torch.no_grad():
         outs = net(images)
-    s, l, hm, ll = _maps(net.KIND, outs)
-    dets, _, keep = _run_batch(s, l, K, lm_heat=hm, lm_loc=ll, nms_thresh=nms_thresh)
-    return dets, keep
+    return _maps(net.KIND, outs)
 
 
-def _graph_replay(net, tag, image, K, nms_thresh, eager, to_host=True):
-    """Replays (capturing on the first call) one hipGraph of eager(net, image, K, nms_thresh) -> (dets, keep) device tensors
-    and returns the two results in pinned host tensors, valid until the next call.  One cache per network, shared by
-    detect(), detect_batch() and detect_pyramid(): keyed by (tag, input shape, input dtype, K, threshold, compute dtype),
-    re-captured when the weight signature changes, at most _MAX_GRAPHS entries (LRU).
+def _detect_eager(K, nms_thresh):
+    def eager(net, image):
+        s, l, hm, ll = _forward_maps(net, image)
+        dets, _, keep = _run(s, l, image.size(2), image.size(3), K, lm_heat=hm, lm_loc=ll, nms_thresh=nms_thresh)
+        return dets, keep
+    return eager
 
-    to_host=False (detect_pyramid's 'level' and 'level_thresh' entries): nothing is copied and nothing waits -- the replay is queued and the entry's
-    own device (dets, keep) are returned, valid in stream order until the entry's next replay.
 
-    to_host='second' (detect_batch_thresh's entries, K = (max_dets, score_thresh)): only the second result, the counts, is copied
-    by the graph; the first, the packed arena, is returned as the entry's device tensor -- how much of it to fetch depends on the
-    counts, and a copy of a size that depends on device data cannot be a graph node.
+def _detect_batch_eager(K, nms_thresh):
+    def eager(net, images):
+        s, l, hm, ll = _forward_maps(net, images)
+        dets, _, keep = _run_batch(s, l, K, lm_heat=hm, lm_loc=ll, nms_thresh=nms_thresh)
+        return dets, keep
+    return eager
 
-    eager may return more than two tensors (detect_plate_crops' entries, K = (K, ow, oh, crops to the host)); to_host is then a
-    tuple with one flag per result -- copied to pinned memory by the graph, or returned as the entry's device tensor."""
+
+def _use_graph(net):
+    """eval mode replays captured hipGraphs; train mode and DBX_GRAPH=0 run the same launches eagerly"""
+    import os
+    return not net.training and os.environ.get('DBX_GRAPH', '1') != '0'
+
+
+def _run_chunk(net, tag, x, key, eager, host):
+    """eager(net, x) -> a tuple of device tensors, through _graph_replay where _use_graph says so (and x is on the device); either way
+    the results whose `host` flag is set come back as host tensors, the others as device tensors."""
+    if x.is_cuda and _use_graph(net):
+        return _graph_replay(net, tag, x, key, eager, host)
+    return tuple(r.cpu() if f else r for r, f in zip(eager(net, x), host))
+
+
+def _graph_replay(net, tag, x, key, eager, host):
+    """Replays (capturing on the first call) one hipGraph of eager(net, x) -> a tuple of device tensors.  One cache per network, shared
+    by every inference entry point: keyed by (tag, input shape, input dtype) + key + (compute dtype,), re-captured when the weight
+    signature changes, at most _MAX_GRAPHS entries (LRU).
+
+    eager is a closure that holds its own parameters; key is a hashable tuple in which the caller names everything a replay bakes in
+    (kernel arguments such as K and the thresholds, buffer addresses, the serial of an evaluator or tracker, the first stream): two calls
+    that differ in any of it must differ in key, or the second replays a stale graph.
+
+    host: one bool per result.  A flagged result is copied to pinned memory by the graph and returned as that pinned host tensor, valid
+    until the entry's next replay; an unflagged one is returned as the entry's own device tensor (or whatever eager returned in its
+    place: the entry keeps it alive), valid in stream order until the entry's next replay -- e.g. detect_batch_thresh's arena, of which
+    the counts decide how much to fetch: a copy of a size that depends on device data cannot be a graph node.  The stream is synchronised
+    iff a flag is set; with none set nothing is copied and nothing waits (detect_pyramid's levels)."""
     import collections
     cache = net.__dict__.setdefault('_detect_graphs', collections.OrderedDict())
     # weight signature: versions + storage addresses of every parameter (a replay reads the packed copies made at capture).
@@ -145,16 +179,15 @@ def _graph_replay(net, tag, image, K, nms_thresh, eager, to_host=True):
         net.__dict__['_detect_pdicts'] = pd
     pd[0] -= 1
     sig = (kids,) + tuple([(p._version, p.data_ptr()) for d in pd[1] for p in d.values() if p is not None])
-    key = (tag, tuple(image.shape), image.dtype, K, float(nms_thresh), net.resolved_dtype(False))
+    key = (tag, tuple(x.shape), x.dtype) + tuple(key) + (net.resolved_dtype(False),)
     ent = cache.get(key)
     if ent is None or ent[0] != sig:
-        static_in = image.clone()
+        static_in = x.clone()
         for _ in range(2):                       # warm: workspace plan, packed weights, scratch buffers, kernel attributes
-            warm = eager(net, static_in, K, nms_thresh)
-        flags = to_host if isinstance(to_host, tuple) else (to_host is True, bool(to_host))      # True: both; 'second': the second
-        assert len(flags) == len(warm)
+            warm = eager(net, static_in)
+        assert len(host) == len(warm)
         pinned = tuple(torch.empty(w.shape, dtype=w.dtype).pin_memory() if f else None       # (pinned allocation is not capturable)
-                       for w, f in zip(warm, flags))
+                       for w, f in zip(warm, host))
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         # No cyclic garbage collection DURING the capture: a dead network (modules sit in reference cycles) takes its cached graphs
@@ -166,7 +199,7 @@ def _graph_replay(net, tag, image, K, nms_thresh, eager, to_host=True):
         gc.disable()
         try:
             with torch.cuda.graph(g):
-                outs = tuple(eager(net, static_in, K, nms_thresh))
+                outs = tuple(eager(net, static_in))
                 # the result copies are graph nodes too (pinned destinations): one replay + one stream sync per call
                 # instead of two blocking .cpu() calls with their launch round trips (~60 us of idle GPU per call)
                 for h, o in zip(pinned, outs):
@@ -184,9 +217,9 @@ def _graph_replay(net, tag, image, K, nms_thresh, eager, to_host=True):
             cache.popitem(last=False)
     cache.move_to_end(key)
     _, g, static_in, outs, _refs, pinned = ent
-    static_in.copy_(image)
+    static_in.copy_(x)
     g.replay()
-    if not to_host:
+    if not any(host):
         return outs
     torch.cuda.current_stream().synchronize()
     return tuple(o if h is None else h for o, h in zip(outs, pinned))
@@ -199,17 +232,9 @@ def detect(net, image, K=10, nms_thresh=0.4):
 
     In eval mode the ~25 launches of one image are captured into a hipGraph per (shape, K, dtype, weight version) and
     replayed (the single-image path is launch-bound: 0.8 ms eager vs the kernels' own time); DBX_GRAPH=0 keeps it eager."""
-    import os
     assert image.dim() == 4 and image.size(0) == 1
-    use_graph = image.is_cuda and not net.training and os.environ.get('DBX_GRAPH', '1') != '0'
-    if not use_graph:
-        dets, keep = _detect_eager(net, image, K, nms_thresh)
-    else:
-        h_dets, h_keep = _graph_replay(net, 'detect', image, K, nms_thresh, _detect_eager)
-        k = h_keep.numpy()
-        return h_dets.numpy().copy(), [int(v) for v in k[1:1 + int(k[0])]]
-    k = keep.cpu().numpy()
-    return dets.cpu().numpy(), [int(v) for v in k[1:1 + int(k[0])]]
+    h_dets, h_keep = _run_chunk(net, 'detect', image, (K, float(nms_thresh)), _detect_eager(K, nms_thresh), (True, True))
+    return h_dets.numpy().copy(), _keep_list(h_keep.numpy())
 
 
 def _batch_of(x, what, fn='detect_batch'):
@@ -224,16 +249,28 @@ def _batch_of(x, what, fn='detect_batch'):
     return x
 
 
+def _on_device(x):
+    return (x if x.is_cuda else x.cuda()).contiguous()
+
+
+def _frame_count(fn, images):
+    return len(images) if isinstance(images, (list, tuple)) else int(_batch_of(images, 'images', fn).size(0))
+
+
+def _one_shape(fn, images, with_dtype):
+    """RuntimeError when the tensors of a list of frames differ in shape (with_dtype: or in dtype): stream j is image j, so a list
+    cannot be regrouped by shape as detect_batch does"""
+    if isinstance(images, (list, tuple)):
+        shapes = {(tuple(im.shape[-3:]), im.dtype if with_dtype else None) for im in images if torch.is_tensor(im)}
+        if len(shapes) > 1:
+            raise RuntimeError('%s: the frames of a list must have one shape%s (stream j is image j), got %s'
+                               % (fn, ' and dtype' if with_dtype else '', sorted(str(s[0]) for s in shapes)))
+
+
 def _detect_chunk(net, x, K, nms_thresh):
-    import os
-    x = (x if x.is_cuda else x.cuda()).contiguous()
-    if not net.training and os.environ.get('DBX_GRAPH', '1') != '0':
-        h_dets, h_keep = _graph_replay(net, 'batch', x, K, nms_thresh, _detect_batch_eager)
-    else:
-        dets, keep = _detect_batch_eager(net, x, K, nms_thresh)
-        h_dets, h_keep = dets.cpu(), keep.cpu()
+    h_dets, h_keep = _run_chunk(net, 'batch', x, (K, float(nms_thresh)), _detect_batch_eager(K, nms_thresh), (True, True))
     d, k = h_dets.numpy(), h_keep.numpy()
-    return [(d[b].copy(), [int(v) for v in k[b, 1:1 + int(k[b, 0])]]) for b in range(d.shape[0])]
+    return [(d[b].copy(), _keep_list(k[b])) for b in range(d.shape[0])]
 
 
 def detect_batch(net, images, K=10, nms_thresh=0.4, max_batch=32):
@@ -251,7 +288,7 @@ def detect_batch(net, images, K=10, nms_thresh=0.4, max_batch=32):
 
 def _detect_many(fn, images, max_batch, chunk, with_index=False):
     """detect_batch's walk over a batch tensor or a list of single images: chunk(x) -> list of per-image results for every chunk of at
-    most max_batch same-shape images, results in input order.  Every check runs before the first chunk.  with_index: chunk(x, idx) also
+    most max_batch same-shape images (x a contiguous device tensor), results in input order.  Every check runs before the first chunk.  with_index: chunk(x, idx) also
     gets the input positions of the chunk's images (evaluate_batch finds their ground truth by them)."""
     if max_batch < 1:
         raise RuntimeError('%s: max_batch=%d must be positive' % (fn, max_batch))
@@ -262,6 +299,7 @@ def _detect_many(fn, images, max_batch, chunk, with_index=False):
         out = []
         for i in range(0, x.size(0), max_batch):
             part = x[i:i + max_batch]
+            part = _on_device(part)
             out += chunk(part, list(range(i, i + part.size(0)))) if with_index else chunk(part)
         return out
     if len(images) == 0:
@@ -299,34 +337,28 @@ def _check_thresh(fn, score_thresh, max_dets):
     ok = isinstance(score_thresh, (int, float, np.integer, np.floating)) and not isinstance(score_thresh, (bool, np.bool_))
     if not ok or not np.isfinite(float(score_thresh)):
         raise RuntimeError('%s: score_thresh=%r must be a finite number' % (fn, score_thresh))
-    if isinstance(max_dets, (bool, np.bool_)) or not isinstance(max_dets, (int, np.integer)) or not 1 <= max_dets <= _THRESH_MAX_DETS:
+    if not _integer(max_dets) or not 1 <= max_dets <= _THRESH_MAX_DETS:
         raise RuntimeError('%s: max_dets=%r must be an integer in 1..%d' % (fn, max_dets, _THRESH_MAX_DETS))
     return float(np.float32(score_thresh)), int(max_dets)
 
 
-def _run_thresh_batch(score_map, loc_map, score_thresh, max_dets, lm_heat=None, lm_loc=None, nms_thresh=0.4):
-    """dbx_detect_thresh_batch over [B,C,rows,cols] maps with the keep lists behind the packed rows: (arena uint8, topk int64
-    [B * max_dets], counts int32 [3 B + 1]) device tensors; _unpack_thresh reads them."""
-    B, _, rows, cols = score_map.shape
-    assert score_map.size(1) == 1 and loc_map.size() == torch.Size([B, 4, rows, cols])
-    if lm_heat is not None:
-        assert lm_heat.size() == torch.Size([B, 4, rows, cols])
-    if lm_loc is not None:
-        assert lm_loc.size() == torch.Size([B, 8, rows, cols])
-    dev = score_map.device if score_map.is_cuda else torch.device('cuda')
-
-    def f(t):
-        return None if t is None else t.detach().to(dev, torch.float32).contiguous()
-    s, l, hm, ll = f(score_map), f(loc_map), f(lm_heat), f(lm_loc)
-    dc = 5 if (hm is None and ll is None) else 13
-    arena = torch.empty(B * max_dets * dc * 8 + B * (max_dets + 1) * 4, dtype=torch.uint8, device=dev)
+def _run_thresh_batch(score_map, loc_map, score_thresh, max_dets, lm_heat=None, lm_loc=None, nms_thresh=0.4, lists_behind_rows=True):
+    """dbx_detect_thresh_batch over [B,C,rows,cols] maps: (rows buffer, keep buffer, counts int32 [3 B + 1]) device tensors, packed.
+    lists_behind_rows: both buffers are ONE uint8 arena with the keep lists right behind the packed rows, which _unpack_thresh reads;
+    otherwise the rows are float64 [B * max_dets, 5|13] and the lists int32 [B * (max_dets + 1)], tensors of their own."""
+    s, l, hm, ll, B, rows, cols, dc, dev = _decode_inputs(score_map, loc_map, lm_heat, lm_loc)
+    if lists_behind_rows:
+        dets = keep = torch.empty(B * max_dets * dc * 8 + B * (max_dets + 1) * 4, dtype=torch.uint8, device=dev)
+    else:
+        dets = torch.empty((B * max_dets, dc), dtype=torch.float64, device=dev)
+        keep = torch.empty(B * (max_dets + 1), dtype=torch.int32, device=dev)
     topk = torch.empty(B * max_dets, dtype=torch.int64, device=dev)
     counts = torch.empty(3 * B + 1, dtype=torch.int32, device=dev)
     L = _lib.lib()
     scratch = torch.empty(L.dbx_detect_thresh_batch_scratch_bytes(B, rows, cols, max_dets), dtype=torch.uint8, device=dev)
     check(L.dbx_detect_thresh_batch(ptr(s), ptr(l), ptr(hm), ptr(ll), B, rows, cols, float(score_thresh), max_dets, float(nms_thresh),
-                                    ptr(arena), dc, ptr(topk), ptr(arena), ptr(counts), ptr(scratch), stream_ptr()))
-    return arena, topk, counts
+                                    ptr(dets), dc, ptr(topk), ptr(keep), ptr(counts), ptr(scratch), stream_ptr()))
+    return dets, keep, counts
 
 
 def _thresh_fetch_bytes(counts, dc):
@@ -335,50 +367,58 @@ def _thresh_fetch_bytes(counts, dc):
     return int(counts[3 * B]) * (dc * 8 + 4) + B * 4
 
 
-def _unpack_thresh(counts, arena, dc, with_totals):
-    """per image (dets [n_b, dc] float64, keep list[, pixels above the threshold]) from host arrays: the counts and the fetched arena"""
-    B = (counts.shape[0] - 1) // 3
-    prefix = counts[2 * B:]
-    total = int(prefix[B])
-    rows = arena[:total * dc * 8].view(np.float64).reshape(total, dc)
-    lists = arena[total * dc * 8:total * dc * 8 + (total + B) * 4].view(np.int32)
+def _unpack_packed(prefix, rows, lists, dc):
+    """Per image (dets [n_b, dc] float64, keep list) from host arrays in the packed layout of dbx_detect_thresh_batch and
+    dbx_merge_nms_thresh_batch: with P = prefix, the [B + 1] running sum of the row counts, image b owns rows P[b] .. P[b + 1] - 1
+    (n_b = P[b + 1] - P[b]) and the list [count, idx...] at word P[b] + b.  rows: the uint8 arena or a float64 array of at least
+    P[B] rows; lists: an int32 array, or None for the lists right behind the rows in the arena."""
+    B, total = prefix.shape[0] - 1, int(prefix[-1])
+    if lists is None:
+        lists = rows[total * dc * 8:total * dc * 8 + (total + B) * 4].view(np.int32)
+    if rows.dtype == np.uint8:
+        rows = rows[:total * dc * 8].view(np.float64)
+    rows = rows.reshape(-1)[:total * dc].reshape(total, dc)
     out = []
     for b in range(B):
-        p, n = int(prefix[b]), int(counts[2 * b])
-        k = lists[p + b:p + b + n + 1]
-        r = (rows[p:p + n].copy(), [int(v) for v in k[1:1 + int(k[0])]])
-        out.append(r + (int(counts[2 * b + 1]),) if with_totals else r)
+        p, n = int(prefix[b]), int(prefix[b + 1] - prefix[b])
+        out.append((rows[p:p + n].copy(), _keep_list(lists[p + b:p + b + n + 1])))
     return out
 
 
-def _thresh_batch_eager(net, images, cap_t, nms_thresh):
-    with torch.no_grad():
-        outs = net(images)
-    s, l, hm, ll = _maps(net.KIND, outs)
-    arena, _, counts = _run_thresh_batch(s, l, cap_t[1], cap_t[0], lm_heat=hm, lm_loc=ll, nms_thresh=nms_thresh)
-    return arena, counts
+def _unpack_thresh(counts, arena, dc, with_totals):
+    """per image (dets [n_b, dc] float64, keep list[, pixels above the threshold]) from host arrays: the counts and the fetched arena"""
+    B = (counts.shape[0] - 1) // 3
+    out = _unpack_packed(counts[2 * B:], arena, None, dc)
+    return [r + (int(counts[2 * b + 1]),) for b, r in enumerate(out)] if with_totals else out
+
+
+def _thresh_batch_eager(score_thresh, max_dets, nms_thresh):
+    def eager(net, images):
+        s, l, hm, ll = _forward_maps(net, images)
+        arena, _, counts = _run_thresh_batch(s, l, score_thresh, max_dets, lm_heat=hm, lm_loc=ll, nms_thresh=nms_thresh)
+        return arena, counts
+    return eager
+
+
+def _pinned(net, nbytes):
+    """the network's grow-only pinned staging buffer, at least nbytes long: it grows to the largest fetch seen, never to an arena's
+    capacity"""
+    pin = net.__dict__.get('_thresh_pinned')
+    if pin is None or pin.numel() < nbytes:
+        pin = net.__dict__['_thresh_pinned'] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8).pin_memory()
+    return pin
 
 
 def _thresh_chunk(net, x, score_thresh, max_dets, nms_thresh, with_totals):
-    import os
-    x = (x if x.is_cuda else x.cuda()).contiguous()
-    dc = 5 if net.KIND == 'DenseBox' else 13
-    if not net.training and os.environ.get('DBX_GRAPH', '1') != '0':
-        arena, h_counts = _graph_replay(net, 'thresh', x, (max_dets, score_thresh), nms_thresh, _thresh_batch_eager, to_host='second')
-        counts = h_counts.numpy().copy()
-        nbytes = _thresh_fetch_bytes(counts, dc)
-        pin = net.__dict__.get('_thresh_pinned')
-        if pin is None or pin.numel() < nbytes:                  # grows to the largest fetch seen, never to the arena's capacity
-            pin = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8).pin_memory()
-            net.__dict__['_thresh_pinned'] = pin
-        pin[:nbytes].copy_(arena[:nbytes], non_blocking=True)    # the ONE copy whose size the counts decide, behind the replay
-        torch.cuda.current_stream().synchronize()
-        host = pin[:nbytes].numpy().copy()
-    else:
-        arena, counts = _thresh_batch_eager(net, x, (max_dets, score_thresh), nms_thresh)
-        counts = counts.cpu().numpy()
-        host = arena[:_thresh_fetch_bytes(counts, dc)].cpu().numpy()
-    return _unpack_thresh(counts, host, dc, with_totals)
+    dc = _det_cols(net)
+    arena, counts = _run_chunk(net, 'thresh', x, ((max_dets, score_thresh), float(nms_thresh)),
+                               _thresh_batch_eager(score_thresh, max_dets, nms_thresh), (False, True))
+    counts = counts.numpy().copy()
+    nbytes = _thresh_fetch_bytes(counts, dc)
+    pin = _pinned(net, nbytes)
+    pin[:nbytes].copy_(arena[:nbytes], non_blocking=True)        # the ONE copy whose size the counts decide, behind the replay
+    torch.cuda.current_stream().synchronize()
+    return _unpack_thresh(counts, pin[:nbytes].numpy().copy(), dc, with_totals)
 
 
 def detect_batch_thresh(net, images, score_thresh, max_dets=1024, nms_thresh=0.4, max_batch=32, with_totals=False):
@@ -431,32 +471,29 @@ def detect_plates(net, images, K=10, nms_thresh=0.4, max_batch=32, *, region, sc
     from . import rectify
     rectify.check_region('detect_plates', region)
     tc = _thresh_or_topk('detect_plates', K, score_thresh, max_dets)
-    if net.KIND == 'DenseBox':
-        raise RuntimeError('detect_plates: DenseBox rows have no landmarks to rectify; use DenseBoxLM or DenseBoxLMLOC')
+    _require_landmarks('detect_plates', net)
     host, kinds = rectify.host_images('detect_plates', images, 3)
     if torch.is_tensor(images):                    # one upload of the batch; the forward and the warp read the same device copy
-        x = (images if images.is_cuda else images.cuda()).contiguous()
+        x = _on_device(images)
         dev = list(x.unbind(0))
-        res = detect_batch(net, x, K, nms_thresh, max_batch) if tc is None else detect_batch_thresh(net, x, tc[0], tc[1], nms_thresh, max_batch)
     else:
-        dev = rectify.to_device(images, host)
-        res = detect_batch(net, dev, K, nms_thresh, max_batch) if tc is None else detect_batch_thresh(net, dev, tc[0], tc[1], nms_thresh, max_batch)
+        x = dev = rectify.to_device(images, host)
+    res = detect_batch(net, x, K, nms_thresh, max_batch) if tc is None else detect_batch_thresh(net, x, tc[0], tc[1], nms_thresh, max_batch)
     quads = [[[[d[k, 5], d[k, 6]], [d[k, 7], d[k, 8]], [d[k, 9], d[k, 10]], [d[k, 11], d[k, 12]]] for k in keep] for d, keep in res]
     plates = rectify._warp_batch(dev, kinds, quads, region)
     return [(d, keep, p) for (d, keep), p in zip(res, plates)]
 
 
-def _plate_crops_eager():
+def _plate_crops_eager(K, ow, oh, nms_thresh):
     """The eager function of detect_plate_crops' chunks: forward, dbx_detect_batch, dbx_plate_crops_batch -> (dets, keep, crops, ok,
     frame table) device tensors.  The crop launch reads the pixels of `images` (the graph's static input under capture), the quads at
     dets + 5 and the kept rows in keep.  The frame table is the one thing that comes from the host: it is uploaded on the first call for
     a tensor (the warm-up, outside the capture) and reused for the same address afterwards; the graph entry keeps it with the results."""
     from . import rectify
-    tables = {}
+    detect, tables = _detect_batch_eager(K, nms_thresh), {}
 
-    def eager(net, images, kt, nms_thresh):
-        K, ow, oh = kt[:3]
-        dets, keep = _detect_batch_eager(net, images, K, nms_thresh)
+    def eager(net, images):
+        dets, keep = detect(net, images)
         B, dc = int(dets.size(0)), int(dets.size(2))
         key = (images.data_ptr(), tuple(images.shape))
         table = tables.get(key)
@@ -468,23 +505,15 @@ def _plate_crops_eager():
 
 
 def _plate_crops_chunk(net, x, K, ow, oh, nms_thresh, host_crops):
-    import os
-    x = (x if x.is_cuda else x.cuda()).contiguous()
-    kt = (K, ow, oh, host_crops)
-    if not net.training and os.environ.get('DBX_GRAPH', '1') != '0':
-        d, k, crops, ok, _ = _graph_replay(net, 'plate_crops', x, kt, nms_thresh, _plate_crops_eager(),
-                                           to_host=(True, True, host_crops, True, False))
-    else:
-        d, k, crops, ok, _ = _plate_crops_eager()(net, x, kt, nms_thresh)
-        d, k, ok = d.cpu(), k.cpu(), ok.cpu()
-        crops = crops.cpu() if host_crops else crops
+    d, k, crops, ok, _ = _run_chunk(net, 'plate_crops', x, ((K, ow, oh, host_crops), float(nms_thresh)),
+                                    _plate_crops_eager(K, ow, oh, nms_thresh), (True, True, host_crops, True, False))
     d, k, ok = d.numpy(), k.numpy(), ok.numpy()
     out = []
     for b in range(d.shape[0]):
-        n = int(k[b, 0])
+        keep = _keep_list(k[b])
         # every result owns its memory (a graph entry's buffers are overwritten by its next replay): crops by a clone, device to device
         # for CUDA frames
-        out.append((d[b].copy(), [int(v) for v in k[b, 1:1 + n]], crops[b, :n].clone(), ok[b, :n] != 0))
+        out.append((d[b].copy(), keep, crops[b, :len(keep)].clone(), ok[b, :len(keep)] != 0))
     return out
 
 
@@ -512,12 +541,11 @@ def detect_plate_crops(net, images, *, size, K=10, nms_thresh=0.4, max_batch=32)
     design (most of them empty, or a compaction pass); use detect_batch_thresh and rectify.plate_crops_batch for it."""
     from . import rectify
     ow, oh = rectify._crop_size('detect_plate_crops', size)
-    if net.KIND == 'DenseBox':
-        raise RuntimeError('detect_plate_crops: DenseBox rows have no landmarks to rectify; use DenseBoxLM or DenseBoxLMLOC')
+    _require_landmarks('detect_plate_crops', net)
     host, kinds = rectify.host_images('detect_plate_crops', images, 3)
     host_crops = any(k != 'cuda' for k in kinds)
     if torch.is_tensor(images):                    # one upload of the batch; the forward and the warp read the same device copy
-        x = (images if images.is_cuda else images.cuda()).contiguous()
+        x = _on_device(images)
     else:
         x = rectify.to_device(images, host)
     res = _detect_many('detect_plate_crops', x, max_batch, lambda c: _plate_crops_chunk(net, c, K, ow, oh, nms_thresh, host_crops))
@@ -552,7 +580,7 @@ def detect_batch_resized(net, images, size=720, K=10, nms_thresh=0.4, max_batch=
     in its place (K is then ignored; a non-default K together with a threshold raises), and dets has n_b rows."""
     from . import rectify, resize
     tc = _thresh_or_topk('detect_batch_resized', K, score_thresh, max_dets)
-    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or size < 4 or size % 4:
+    if not _integer(size) or size < 4 or size % 4:
         raise RuntimeError('detect_batch_resized: size=%r must be a positive multiple of 4 (the maps are size / 4)' % (size,))
     host, _ = rectify.host_images('detect_batch_resized', images, 3)
     x = resize._pad_resize_device(rectify.to_device(images, host), int(size))
@@ -576,11 +604,20 @@ _MERGE_MAX_ROWS = 4096           # dbx_merge_nms_batch's bound on levels * K
 
 def _check_pyramid_sizes(sizes):
     ok = isinstance(sizes, (list, tuple)) and 1 <= len(sizes) <= _PYRAMID_MAX_LEVELS
-    ok = ok and all(isinstance(s, (int, np.integer)) and not isinstance(s, (bool, np.bool_)) and s >= 4 and s % 4 == 0 for s in sizes)
+    ok = ok and all(_integer(s) and s >= 4 and s % 4 == 0 for s in sizes)
     if not ok or len({int(s) for s in sizes}) != len(sizes):
         raise RuntimeError('detect_pyramid: sizes=%r must be 1 to %d distinct positive multiples of 4 (the maps are size / 4; every '
                            'level owns a cached graph shape)' % (sizes, _PYRAMID_MAX_LEVELS))
     return [int(s) for s in sizes]
+
+
+def _xform_table(xform, levels, b):
+    """the host array of dbx_merge_xform [levels][b] from xform [levels][b] (scale, off_x, off_y) triples"""
+    xf = (_lib.MergeXform * (levels * b))()
+    for l in range(levels):
+        for i in range(b):
+            xf[l * b + i].scale, xf[l * b + i].off_x, xf[l * b + i].off_y = xform[l][i]
+    return xf
 
 
 def _merge_nms(level_dets, xform, nms_thresh, out_dets, out_keep):
@@ -588,10 +625,7 @@ def _merge_nms(level_dets, xform, nms_thresh, out_dets, out_keep):
     triples, out_dets [b, L * K, dc] / out_keep [b, L * K + 1] device tensors (views of larger ones are fine: both are dense)."""
     levels, (b, K, dc) = len(level_dets), level_dets[0].shape
     ptrs = (C.c_void_p * levels)(*[t.data_ptr() for t in level_dets])
-    xf = (_lib.MergeXform * (levels * b))()
-    for l in range(levels):
-        for i in range(b):
-            xf[l * b + i].scale, xf[l * b + i].off_x, xf[l * b + i].off_y = xform[l][i]
+    xf = _xform_table(xform, levels, b)
     L = _lib.lib()
     nbytes = L.dbx_merge_nms_batch_workspace_bytes(levels, b, K)
     if nbytes < 0:
@@ -603,18 +637,7 @@ def _merge_nms(level_dets, xform, nms_thresh, out_dets, out_keep):
 def _run_thresh_rows(score_map, loc_map, score_thresh, max_dets, lm_heat=None, lm_loc=None):
     """dbx_thresh_rows_batch over [B,C,rows,cols] maps: (dets float64 [B, max_dets, 5|13], topk int64 [B, max_dets], counts int32 [B, 2])
     device tensors in slot layout; only the first counts[b, 0] rows of image b are written."""
-    B, _, rows, cols = score_map.shape
-    assert score_map.size(1) == 1 and loc_map.size() == torch.Size([B, 4, rows, cols])
-    if lm_heat is not None:
-        assert lm_heat.size() == torch.Size([B, 4, rows, cols])
-    if lm_loc is not None:
-        assert lm_loc.size() == torch.Size([B, 8, rows, cols])
-    dev = score_map.device if score_map.is_cuda else torch.device('cuda')
-
-    def f(t):
-        return None if t is None else t.detach().to(dev, torch.float32).contiguous()
-    s, l, hm, ll = f(score_map), f(loc_map), f(lm_heat), f(lm_loc)
-    dc = 5 if (hm is None and ll is None) else 13
+    s, l, hm, ll, B, rows, cols, dc, dev = _decode_inputs(score_map, loc_map, lm_heat, lm_loc)
     dets = torch.empty((B, max_dets, dc), dtype=torch.float64, device=dev)
     topk = torch.empty((B, max_dets), dtype=torch.int64, device=dev)
     counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
@@ -625,12 +648,12 @@ def _run_thresh_rows(score_map, loc_map, score_thresh, max_dets, lm_heat=None, l
     return dets, topk, counts
 
 
-def _thresh_rows_eager(net, images, cap_t, nms_thresh):
-    with torch.no_grad():
-        outs = net(images)
-    s, l, hm, ll = _maps(net.KIND, outs)
-    dets, _, counts = _run_thresh_rows(s, l, cap_t[1], cap_t[0], lm_heat=hm, lm_loc=ll)
-    return dets, counts
+def _thresh_rows_eager(score_thresh, max_dets):
+    def eager(net, images):
+        s, l, hm, ll = _forward_maps(net, images)
+        dets, _, counts = _run_thresh_rows(s, l, score_thresh, max_dets, lm_heat=hm, lm_loc=ll)
+        return dets, counts
+    return eager
 
 
 def _merge_nms_thresh(level_dets, level_counts, xform, nms_thresh, arena, out_counts):
@@ -640,10 +663,7 @@ def _merge_nms_thresh(level_dets, level_counts, xform, nms_thresh, arena, out_co
     levels, (b, cap, dc) = len(level_dets), level_dets[0].shape
     dp = (C.c_void_p * levels)(*[t.data_ptr() for t in level_dets])
     cp = (C.c_void_p * levels)(*[t.data_ptr() for t in level_counts])
-    xf = (_lib.MergeXform * (levels * b))()
-    for l in range(levels):
-        for i in range(b):
-            xf[l * b + i].scale, xf[l * b + i].off_x, xf[l * b + i].off_y = xform[l][i]
+    xf = _xform_table(xform, levels, b)
     L = _lib.lib()
     ws = torch.empty(L.dbx_merge_nms_thresh_batch_workspace_bytes(levels, b, cap), dtype=torch.uint8, device=arena.device)
     check(L.dbx_merge_nms_thresh_batch(dp, cp, xf, levels, b, cap, dc, float(nms_thresh), ptr(arena), ptr(arena), ptr(out_counts), ptr(ws),
@@ -664,25 +684,18 @@ def _pyramid_thresh_fetch_bytes(counts, levels, dc):
 def _unpack_pyramid_thresh(counts, arena, levels, dc, with_levels):
     """per frame (dets [m_b, dc] float64, keep list[, rows per level]) from host arrays: a chunk's merge counts and its fetched arena"""
     b = (counts.shape[0] - 1) // (2 * levels + 1)
-    pairs, prefix = counts[:2 * b * levels].reshape(b, levels, 2), counts[2 * b * levels:]
-    total = int(prefix[b])
-    rows = arena[:total * dc * 8].view(np.float64).reshape(total, dc)
-    lists = arena[total * dc * 8:total * dc * 8 + (total + b) * 4].view(np.int32)
-    out = []
-    for i in range(b):
-        p, m = int(prefix[i]), int(prefix[i + 1] - prefix[i])
-        k = lists[p + i:p + i + m + 1]
-        r = (rows[p:p + m].copy(), [int(v) for v in k[1:1 + int(k[0])]])
-        out.append(r + (pairs[i, :, 0].astype(np.int64),) if with_levels else r)
+    out = _unpack_packed(counts[2 * b * levels:], arena, None, dc)
+    if with_levels:
+        pairs = counts[:2 * b * levels].reshape(b, levels, 2)
+        out = [r + (pairs[i, :, 0].astype(np.int64),) for i, r in enumerate(out)]
     return out
 
 
-def _pyramid_thresh(net, levels, xform, B, t, cap, nms_thresh, max_batch, graph, with_levels):
+def _pyramid_thresh(net, levels, xform, B, t, cap, nms_thresh, max_batch, with_levels):
     """detect_pyramid's threshold path over the resized levels: everything is queued first, then the counts come to the host, then
     exactly the rows and lists"""
-    nl = len(levels)
-    dc = 5 if net.KIND == 'DenseBox' else 13
-    dev = levels[0].device
+    nl, dc, dev = len(levels), _det_cols(net), levels[0].device
+    eager = _thresh_rows_eager(t, cap)
     spans = [(c0, min(B, c0 + max_batch)) for c0 in range(0, B, max_batch)]
     offs = np.cumsum([0] + [_pyramid_counts_words(c1 - c0, nl) for c0, c1 in spans])
     counts_dev = torch.empty(int(offs[-1]), dtype=torch.int32, device=dev)
@@ -690,11 +703,8 @@ def _pyramid_thresh(net, levels, xform, B, t, cap, nms_thresh, max_batch, graph,
     for (c0, c1), o0, o1 in zip(spans, offs[:-1], offs[1:]):
         rows, cnts = [], []
         for lv in levels:
-            x = lv[c0:c1]
-            if graph:        # the entry's device rows and counts: overwritten by its next replay, queued behind this chunk's merge
-                d, c = _graph_replay(net, 'level_thresh', x, (cap, t), nms_thresh, _thresh_rows_eager, to_host=False)
-            else:
-                d, c = _thresh_rows_eager(net, x, (cap, t), nms_thresh)
+            # (a graph entry's device rows and counts: overwritten by its next replay, queued behind this chunk's merge)
+            d, c = _run_chunk(net, 'level_thresh', lv[c0:c1], ((cap, t), float(nms_thresh)), eager, (False, False))
             rows.append(d)
             cnts.append(c)
         b = c1 - c0
@@ -704,10 +714,7 @@ def _pyramid_thresh(net, levels, xform, B, t, cap, nms_thresh, max_batch, graph,
     counts = counts_dev.cpu().numpy()                                # the first wait of the call
     parts = [counts[int(o0):int(o1)] for o0, o1 in zip(offs[:-1], offs[1:])]
     nbytes = [_pyramid_thresh_fetch_bytes(c, nl, dc) for c in parts]
-    pin = net.__dict__.get('_thresh_pinned')
-    if pin is None or pin.numel() < sum(nbytes):                     # grows to the largest fetch seen, never to the arenas' capacity
-        pin = torch.empty(max(sum(nbytes), 1 << 16), dtype=torch.uint8).pin_memory()
-        net.__dict__['_thresh_pinned'] = pin
+    pin = _pinned(net, sum(nbytes))
     at = np.cumsum([0] + nbytes)
     for arena, a0, nb in zip(arenas, at[:-1], nbytes):
         pin[int(a0):int(a0) + nb].copy_(arena[:nb], non_blocking=True)
@@ -753,27 +760,24 @@ def detect_pyramid(net, images, sizes=(480, 720, 1080), K=10, nms_thresh=0.4, ma
     each level gave (the level of row i follows from its cumulative sum).  The result is bit for bit detect_batch_resized(frames,
     size=s, score_thresh=..., max_dets=..., max_batch=...) per size, the rows of each frame concatenated in the order of `sizes`, and
     decode.NMS over them."""
-    import os
     from . import rectify, resize
     sizes = _check_pyramid_sizes(sizes)
     tc = _thresh_or_topk('detect_pyramid', K, score_thresh, max_dets)
     if tc is not None and len(sizes) * tc[1] > _MERGE_MAX_ROWS:
         raise RuntimeError('detect_pyramid: len(sizes)=%d levels x max_dets=%d rows exceed %d rows per frame'
                            % (len(sizes), tc[1], _MERGE_MAX_ROWS))
-    if isinstance(max_batch, bool) or not isinstance(max_batch, (int, np.integer)) or max_batch < 1:
+    if not _integer(max_batch) or max_batch < 1:
         raise RuntimeError('detect_pyramid: max_batch=%r must be a positive integer' % (max_batch,))
-    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1 or len(sizes) * K > _MERGE_MAX_ROWS:
+    if not _integer(K) or K < 1 or len(sizes) * K > _MERGE_MAX_ROWS:
         raise RuntimeError('detect_pyramid: K=%r must be a positive integer with len(sizes) * K <= %d' % (K, _MERGE_MAX_ROWS))
     host, _ = rectify.host_images('detect_pyramid', images, 3)
     K, max_batch, B, nl = int(K), int(max_batch), len(host), len(sizes)
     dev = rectify.to_device(images, host)
     levels = resize._pad_resize_levels(dev, sizes)
     xform = [[resize.level_xform(im.size(0), im.size(1), s) for im in host] for s in sizes]
-    graph = not net.training and os.environ.get('DBX_GRAPH', '1') != '0'
     if tc is not None:
-        return _pyramid_thresh(net, levels, xform, B, tc[0], tc[1], nms_thresh, max_batch, graph, bool(with_levels))
-    dc = 5 if net.KIND == 'DenseBox' else 13
-    n = nl * K
+        return _pyramid_thresh(net, levels, xform, B, tc[0], tc[1], nms_thresh, max_batch, bool(with_levels))
+    dc, n, eager = _det_cols(net), nl * K, _detect_batch_eager(K, nms_thresh)
     # one device buffer for the whole call: [B][n][dc] float64 rows, then [B][n + 1] int32 keep lists -- a single copy to the host
     nd = B * n * dc * 8
     buf = torch.empty(nd + B * (n + 1) * 4, dtype=torch.uint8, device=dev[0].device)
@@ -782,14 +786,10 @@ def detect_pyramid(net, images, sizes=(480, 720, 1080), K=10, nms_thresh=0.4, ma
         c1 = min(B, c0 + max_batch)
         rows = []
         for lv in levels:
-            x = lv[c0:c1]
-            if graph:        # the entry's device rows: overwritten by its next replay, which is queued behind this chunk's merge
-                d, _ = _graph_replay(net, 'level', x, K, nms_thresh, _detect_batch_eager, to_host=False)
-            else:
-                d, _ = _detect_batch_eager(net, x, K, nms_thresh)
-            rows.append(d)
+            # (a graph entry's device rows: overwritten by its next replay, which is queued behind this chunk's merge)
+            rows.append(_run_chunk(net, 'level', lv[c0:c1], (K, float(nms_thresh)), eager, (False, False))[0])
         _merge_nms(rows, [xf[c0:c1] for xf in xform], nms_thresh, out_dets[c0:c1], out_keep[c0:c1])
     h = buf.cpu()
     d = h[:nd].view(torch.float64).view(B, n, dc).numpy()
     k = h[nd:].view(torch.int32).view(B, n + 1).numpy()
-    return [(d[b].copy(), [int(v) for v in k[b, 1:1 + int(k[b, 0])]]) for b in range(B)]
+    return [(d[b].copy(), _keep_list(k[b])) for b in range(B)]

@@ -15,8 +15,9 @@ import itertools
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, decode as DC
 from ._lib import check, ptr, stream_ptr
+from .decode import _host, _integer
 
 MAX_SLOTS = 4096             # dbx_match_gt_batch's bound on the list positions of a frame
 MAX_GT = 1024                # ... and on the GT boxes of a frame (they live in LDS)
@@ -60,10 +61,6 @@ def precision_recall_at(scores, status, n_gt, score_thresh):
 
 
 # ------------------------------------------------------------------------------------------------------------ host: ground truth
-def _host(a):
-    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-
-
 def _gt_frames(fn, n, gt_boxes, gt_ignore, gt_quads, max_gt):
     """per image (boxes float64 [g, 4], ignore uint8 [g], quads float64 [g, 8] or None), or RuntimeError"""
     for name, v in (('gt_boxes', gt_boxes), ('gt_ignore', gt_ignore), ('gt_quads', gt_quads)):
@@ -206,11 +203,9 @@ class Evaluator:
     _serials = itertools.count()
 
     def __init__(self, capacity=1 << 20, iou_thresh=0.5, max_gt=64, device=None):
-        def integer(v):
-            return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-        if not integer(capacity) or capacity < 1:
+        if not _integer(capacity) or capacity < 1:
             raise RuntimeError('Evaluator: capacity=%r must be a positive integer' % (capacity,))
-        if not integer(max_gt) or not 1 <= max_gt <= MAX_GT:
+        if not _integer(max_gt) or not 1 <= max_gt <= MAX_GT:
             raise RuntimeError('Evaluator: max_gt=%r must be an integer in 1..%d' % (max_gt, MAX_GT))
         if isinstance(iou_thresh, bool) or not isinstance(iou_thresh, (int, float, np.integer, np.floating)) or np.isnan(iou_thresh):
             raise RuntimeError('Evaluator: iou_thresh=%r must be a number' % (iou_thresh,))
@@ -260,44 +255,24 @@ class Evaluator:
 
 # ------------------------------------------------------------------------------------------------------------ net.evaluate_batch
 def _run_thresh_lists(score_map, loc_map, score_thresh, max_dets, lm_heat, lm_loc, nms_thresh):
-    """dbx_detect_thresh_batch with the keep lists in a buffer of their own: (dets float64 [B * max_dets, 5|13], keep int32
-    [B * (max_dets + 1)], counts int32 [3 B + 1]) device tensors, packed"""
-    B, _, rows, cols = score_map.shape
-    dev = score_map.device
-
-    def f(t):
-        return None if t is None else t.detach().to(dev, torch.float32).contiguous()
-    s, l, hm, ll = f(score_map), f(loc_map), f(lm_heat), f(lm_loc)
-    dc = 5 if (hm is None and ll is None) else 13
-    dets = torch.empty((B * max_dets, dc), dtype=torch.float64, device=dev)
-    keep = torch.empty(B * (max_dets + 1), dtype=torch.int32, device=dev)
-    topk = torch.empty(B * max_dets, dtype=torch.int64, device=dev)
-    counts = torch.empty(3 * B + 1, dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    scratch = torch.empty(L.dbx_detect_thresh_batch_scratch_bytes(B, rows, cols, max_dets), dtype=torch.uint8, device=dev)
-    check(L.dbx_detect_thresh_batch(ptr(s), ptr(l), ptr(hm), ptr(ll), B, rows, cols, float(score_thresh), max_dets, float(nms_thresh),
-                                    ptr(dets), dc, ptr(topk), ptr(keep), ptr(counts), ptr(scratch), stream_ptr()))
-    return dets, keep, counts
+    """decode._run_thresh_batch with the keep lists in a buffer of their own (the kernel tests of the matcher and the tracker feed on it)"""
+    return DC._run_thresh_batch(score_map, loc_map, score_thresh, max_dets, lm_heat, lm_loc, nms_thresh, lists_behind_rows=False)
 
 
-def _eval_eager(ev, gtbuf, gt_cols, dry_outside_capture):
-    """The eager function of evaluate_batch's chunks: forward, decode (+ NMS), dbx_match_gt_batch, dbx_eval_append.  kt = ('topk', K, ...)
-    or ('thresh', max_dets, score_thresh, ...).  Under _graph_replay the function also runs twice as a warm-up before the capture: with
-    dry_outside_capture those runs append into a scratch state with capacity 0, so only replays count.  Returns (tally, every tensor the
-    launches read or wrote): a graph entry keeps both, which pins the buffers its replays use."""
-    from . import decode as DC
-
-    def eager(net, images, kt, nms_thresh):
-        with torch.no_grad():
-            outs = net(images)
-        s, l, hm, ll = DC._maps(net.KIND, outs)
+def _eval_eager(ev, gtbuf, gt_cols, K, thresh, nms_thresh, dry_outside_capture):
+    """The eager function of evaluate_batch's chunks: forward, decode (+ NMS), dbx_match_gt_batch, dbx_eval_append.  thresh: None for
+    the top-K decode of K rows, or (score_thresh, max_dets).  Under _graph_replay the function also runs twice as a warm-up before the
+    capture: with dry_outside_capture those runs append into a scratch state with capacity 0, so only replays count.  Returns (tally,
+    every tensor the launches read or wrote): a graph entry keeps both, which pins the buffers its replays use."""
+    def eager(net, images):
+        s, l, hm, ll = DC._forward_maps(net, images)
         B = int(images.size(0))
-        if kt[0] == 'topk':
-            slots, prefix = kt[1], None
+        if thresh is None:
+            slots, prefix = K, None
             dets, _, keep = DC._run_batch(s, l, slots, lm_heat=hm, lm_loc=ll, nms_thresh=nms_thresh)
         else:
-            slots = kt[1]
-            dets, keep, counts = _run_thresh_lists(s, l, kt[2], slots, hm, ll, nms_thresh)
+            slots = thresh[1]
+            dets, keep, counts = DC._run_thresh_batch(s, l, thresh[0], slots, hm, ll, nms_thresh, lists_behind_rows=False)
             prefix = counts[2 * B:]
         dc = int(dets.size(-1))
         status, index, iou, err, tally = _launch_match(dets, dc, B * slots, keep, prefix, B, slots, gtbuf, gt_cols, ev.max_gt, ev.iou_thresh)
@@ -326,32 +301,25 @@ def evaluate_batch(net, images, gt_boxes, *, evaluator, K=10, score_thresh=None,
     mode and its sizes, the evaluator and its buffers, iou_thresh, max_gt, GT columns), nms_thresh, compute dtype); the chunk's ground
     truth is uploaded into a static device buffer of the evaluator that the captured launches read.  Train mode and DBX_GRAPH=0 run the
     same launches eagerly."""
-    import os
-    from . import decode as DC
     fn = 'evaluate_batch'
     if not isinstance(evaluator, Evaluator):
         raise RuntimeError('%s: evaluator must be an evaluate.Evaluator, got %s' % (fn, type(evaluator).__name__))
     tc = DC._thresh_or_topk(fn, K, score_thresh, max_dets)
-    if tc is None and (isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= MAX_SLOTS):
+    if tc is None and (not _integer(K) or not 1 <= K <= MAX_SLOTS):
         raise RuntimeError('%s: K=%r must be an integer in 1..%d' % (fn, K, MAX_SLOTS))
-    if gt_quads is not None and net.KIND == 'DenseBox':
-        raise RuntimeError('%s: DenseBox rows have no landmarks to compare gt_quads with; use DenseBoxLM or DenseBoxLMLOC' % fn)
-    n = len(images) if isinstance(images, (list, tuple)) else int(DC._batch_of(images, 'images', fn).size(0))
-    frames = _gt_frames(fn, n, gt_boxes, gt_ignore, gt_quads, evaluator.max_gt)
+    if gt_quads is not None:
+        DC._require_landmarks(fn, net, 'compare gt_quads with')
+    frames = _gt_frames(fn, DC._frame_count(fn, images), gt_boxes, gt_ignore, gt_quads, evaluator.max_gt)
     gt_cols = 12 if gt_quads is not None else 4
     mode = ('topk', int(K)) if tc is None else ('thresh', tc[1], tc[0])
-    graph = not net.training and os.environ.get('DBX_GRAPH', '1') != '0'
+    dry = DC._use_graph(net)
 
     def chunk(x, idx):
-        x = (x if x.is_cuda else x.cuda()).contiguous()
         records, state = evaluator._buffers(x.device)
         gtbuf = evaluator._gt_static(len(idx), gt_cols)
         gtbuf.copy_(torch.from_numpy(_pack_gt([frames[i] for i in idx], evaluator.max_gt, gt_cols)))      # the chunk's one upload
-        kt = mode + (evaluator.serial, records.data_ptr(), state.data_ptr(), gtbuf.data_ptr(), evaluator.iou_thresh, evaluator.max_gt, gt_cols)
-        eager = _eval_eager(evaluator, gtbuf, gt_cols, graph)
-        if graph:
-            DC._graph_replay(net, 'evaluate', x, kt, nms_thresh, eager, to_host=False)
-        else:
-            eager(net, x, kt, nms_thresh)
+        key = (mode + (evaluator.serial, records.data_ptr(), state.data_ptr(), gtbuf.data_ptr(), evaluator.iou_thresh, evaluator.max_gt,
+                       gt_cols), float(nms_thresh))
+        DC._run_chunk(net, 'evaluate', x, key, _eval_eager(evaluator, gtbuf, gt_cols, int(K), tc, nms_thresh, dry), (False, False))
         return [None] * len(idx)
     DC._detect_many(fn, images, max_batch, chunk, with_index=True)

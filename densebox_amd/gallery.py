@@ -8,9 +8,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, track as TR
+from . import _lib, decode as DC, track as TR
 from ._lib import check, ptr, stream_ptr
-from .track import _integer
+from .decode import _host, _integer
 
 MAX_PIXELS = 16384           # oh * ow of a crop: its luma plane is staged in LDS as 16-bit values
 POLICIES = {'sharpness': 0, 'score': 1}
@@ -148,7 +148,7 @@ def sharpness(crops):
     n, oh, ow, c = (int(v) for v in t.shape)
     if oh < 1 or ow < 1 or oh * ow > MAX_PIXELS:
         raise RuntimeError('sharpness: a crop of %d x %d pixels is not 1..%d pixels' % (ow, oh, MAX_PIXELS))
-    d = (t if t.is_cuda else t.cuda()).contiguous()
+    d = DC._on_device(t)
     out = torch.empty(n, dtype=torch.int64, device=d.device)
     if n:
         check(_lib.lib().dbx_crop_sharpness(ptr(d), n, oh, ow, c, ptr(out), stream_ptr()))
@@ -211,7 +211,7 @@ def update_batch(images, dets, keeps, *, tracker, gallery, stream0=0):
     host_ims, _ = rectify.host_images(fn, images, gallery.channels)
     if len(host_ims) != B:
         raise RuntimeError('%s: %d images for %d entries of dets' % (fn, len(host_ims), B))
-    rows = [TR._host(d).astype(np.float64) for d in dets]
+    rows = [_host(d).astype(np.float64) for d in dets]
     if any(r.ndim != 2 or r.shape[1] != 13 for r in rows):
         raise RuntimeError('%s: every dets entry must be [n, 13] (rows with landmarks); got %s' % (fn, [list(r.shape) for r in rows]))
     lists = [np.asarray(k, np.int64).reshape(-1) for k in keeps]
@@ -242,23 +242,17 @@ def update_batch(images, dets, keeps, *, tracker, gallery, stream0=0):
 
 
 # ------------------------------------------------------------------------------------------------------------ net.track_plate_crops
-def _eager(tr, gal, dry_outside_capture):
-    """The eager function of track_plate_crops' chunks: forward, dbx_detect_batch, dbx_plate_crops_batch, then the three launches of
-    _launch.  kt = (K, first stream, ...).  The frame table is uploaded on the first call for a tensor (a warm-up run, outside the
-    capture) and reused for the same address afterwards, as in detect_plate_crops.  Under _graph_replay the warm-up runs are dry.
-    Returns the tensors that go to the host first, then every other tensor the launches wrote or read: a graph entry keeps them all."""
-    from . import decode as DC, rectify
-    tables = {}
+def _eager(tr, gal, K, stream0, nms_thresh, dry_outside_capture):
+    """The eager function of track_plate_crops' chunks, for the streams from stream0 on: forward, dbx_detect_batch,
+    dbx_plate_crops_batch, then the three launches of _launch.  The frame table is uploaded on the first call for a tensor (a warm-up
+    run, outside the capture) and reused for the same address afterwards, as in detect_plate_crops.  Under _graph_replay the warm-up
+    runs are dry.  Returns the tensors that go to the host first, then every other tensor the launches wrote or read: a graph entry
+    keeps them all."""
+    crops_eager = DC._plate_crops_eager(K, gal.ow, gal.oh, nms_thresh)
 
-    def eager(net, images, kt, nms_thresh):
-        K, stream0 = kt[0], kt[1]
-        dets, keep = DC._detect_batch_eager(net, images, K, nms_thresh)
+    def eager(net, images):
+        dets, keep, crops, ok, table = crops_eager(net, images)
         B, dc = int(dets.size(0)), int(dets.size(2))
-        key = (images.data_ptr(), tuple(images.shape))
-        table = tables.get(key)
-        if table is None:
-            table = tables[key] = rectify.frame_table(list(images.unbind(0)))
-        crops, ok = rectify._crops_launch(table, B, 3, dets.data_ptr() + 5 * 8, dc, K * dc, keep, K, gal.ow, gal.oh, images.device)
         dry = dry_outside_capture and not torch.cuda.is_current_stream_capturing()
         ids, slot, retired, tally = _launch(tr, gal, dets, dc, B * K, keep, B, K, stream0, crops, ok, dry)
         return dets, keep, ids, slot, retired, tally, crops, ok, table
@@ -286,22 +280,13 @@ def track_plate_crops(net, images, *, tracker, gallery, stream0=0, K=10, nms_thr
     chunk's first stream, the tracker, its buffers and parameters, the gallery's buffers and parameters), nms_thresh, compute dtype).
     The capture's warm-up runs advance a scratch copy of the tracker's state and run the gallery launch with commit = 0, so only
     replays count.  Train mode and DBX_GRAPH=0 run the same launches eagerly."""
-    import os
-    from . import decode as DC
     fn = 'track_plate_crops'
-    if net.KIND == 'DenseBox':
-        raise RuntimeError('%s: DenseBox rows have no landmarks to rectify; use DenseBoxLM or DenseBoxLMLOC' % fn)
-    if isinstance(images, (list, tuple)):
-        if any(not torch.is_tensor(im) for im in images):
-            raise RuntimeError('%s: a list of images must hold uint8 [H,W,3] tensors' % fn)
-        dtypes = {im.dtype for im in images}
-        shapes = {tuple(im.shape[-3:]) for im in images}
-        if len(shapes) > 1:
-            raise RuntimeError('%s: the frames of a list must have one shape (stream j is image j), got %s' % (fn, sorted(map(str, shapes))))
-        n = len(images)
-    else:
-        dtypes = {DC._batch_of(images, 'images', fn).dtype}
-        n = int(images.size(0))
+    DC._require_landmarks(fn, net)
+    if isinstance(images, (list, tuple)) and any(not torch.is_tensor(im) for im in images):
+        raise RuntimeError('%s: a list of images must hold uint8 [H,W,3] tensors' % fn)
+    DC._one_shape(fn, images, with_dtype=False)
+    n = DC._frame_count(fn, images)
+    dtypes = {im.dtype for im in images} if isinstance(images, (list, tuple)) else {images.dtype}
     if dtypes != {torch.uint8} and n:
         raise RuntimeError('%s: images must be uint8 [B,H,W,3] frames (the pixels that are cropped), got %s' % (fn, sorted(map(str, dtypes))))
     TR._check_streams(fn, tracker, stream0, n)
@@ -310,16 +295,13 @@ def track_plate_crops(net, images, *, tracker, gallery, stream0=0, K=10, nms_thr
         raise RuntimeError('%s: the gallery has %d channels, the frames 3' % (fn, gallery.channels))
     if not _integer(K) or not 1 <= K <= TR.MAX_SLOTS:
         raise RuntimeError('%s: K=%r must be an integer in 1..%d' % (fn, K, TR.MAX_SLOTS))
-    graph = not net.training and os.environ.get('DBX_GRAPH', '1') != '0'
+    dry = DC._use_graph(net)
 
     def chunk(x, idx):
-        x = (x if x.is_cuda else x.cuda()).contiguous()
+        first = int(stream0) + idx[0]
         state, records = tracker._buffers(x.device)
-        kt = (int(K), int(stream0) + idx[0], tracker.serial, state.data_ptr(), records.data_ptr()) + tracker.params() + gallery._key(x.device)
-        eager = _eager(tracker, gallery, graph)
-        if graph:
-            res = DC._graph_replay(net, 'track_plate_crops', x, kt, nms_thresh, eager, to_host=_HOST)
-        else:
-            res = tuple(r.cpu() if f else r for r, f in zip(eager(net, x, kt, nms_thresh), _HOST))
+        key = ((int(K), first, tracker.serial, state.data_ptr(), records.data_ptr()) + tracker.params() + gallery._key(x.device),
+               float(nms_thresh))
+        res = DC._run_chunk(net, fn, x, key, _eager(tracker, gallery, int(K), first, nms_thresh, dry), _HOST)
         return TR._unpack('topk', res, 13)
     return DC._detect_many(fn, images, max_batch, chunk, with_index=True)

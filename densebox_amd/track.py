@@ -13,8 +13,9 @@ import itertools
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, decode as DC
 from ._lib import check, ptr, stream_ptr
+from .decode import _host, _integer, _keep_list
 
 MAX_SLOTS = 1024             # dbx_track_update_batch's bound on the list positions of a frame (they live in LDS)
 MAX_TRACKS = 256             # ... and on the track slots of a stream (one thread each)
@@ -22,10 +23,6 @@ TRACK = np.dtype([('box', '<f8', (4,)), ('vel', '<f8', (4,)), ('score', '<f8'), 
                   ('age', '<i4'), ('first_frame', '<i4'), ('last_frame', '<i4'), ('best_frame', '<i4')])           # dbx_track
 RECORD = np.dtype([('stream', '<i4'), ('reserved', '<i4'), ('t', TRACK)])                                           # dbx_track_record
 assert TRACK.itemsize == C.sizeof(_lib.Track) == 104 and RECORD.itemsize == C.sizeof(_lib.TrackRecord) == 112
-
-
-def _integer(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 
 
 def _number(v):
@@ -153,10 +150,6 @@ def _check_streams(fn, tracker, stream0, n):
         raise RuntimeError('%s: stream0=%r with %d images does not fit the tracker\'s %d streams' % (fn, stream0, n, tracker.streams))
 
 
-def _host(a):
-    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-
-
 def update_batch(dets, keeps, *, tracker, stream0=0):
     """The host results of any detect_* call tracked with ONE upload, the two launches and one copy back: entry j is the next frame of
     stream stream0 + j.
@@ -199,27 +192,22 @@ def update_batch(dets, keeps, *, tracker, stream0=0):
 
 
 # ------------------------------------------------------------------------------------------------------------ net.track_batch
-def _track_eager(tr, dry_outside_capture):
-    """The eager function of track_batch's chunks: forward, decode (+ NMS), dbx_track_update_batch, dbx_track_append.  kt = ('topk', K,
-    first stream, ...) or ('thresh', max_dets, score_thresh, first stream, ...).  Under _graph_replay the function also runs twice as a
-    warm-up before the capture: with dry_outside_capture those runs advance a scratch copy of the state, so only replays count.  Returns
-    the tensors that go to the host first, then every other tensor the launches wrote: a graph entry keeps them all, which pins the
-    buffers its replays use."""
-    from . import decode as DC, evaluate as EV
-
-    def eager(net, images, kt, nms_thresh):
-        with torch.no_grad():
-            outs = net(images)
-        s, l, hm, ll = DC._maps(net.KIND, outs)
+def _track_eager(tr, K, thresh, stream0, nms_thresh, dry_outside_capture):
+    """The eager function of track_batch's chunks, for the streams from stream0 on: forward, decode (+ NMS), dbx_track_update_batch,
+    dbx_track_append.  thresh: None for the top-K decode of K rows, or (score_thresh, max_dets).  Under _graph_replay the function also
+    runs twice as a warm-up before the capture: with dry_outside_capture those runs advance a scratch copy of the state, so only replays
+    count.  Returns the tensors that go to the host first, then every other tensor the launches wrote: a graph entry keeps them all,
+    which pins the buffers its replays use."""
+    def eager(net, images):
+        s, l, hm, ll = DC._forward_maps(net, images)
         B = int(images.size(0))
         dry = dry_outside_capture and not torch.cuda.is_current_stream_capturing()
-        if kt[0] == 'topk':
-            slots, stream0 = kt[1], kt[2]
-            dets, _, keep = DC._run_batch(s, l, slots, lm_heat=hm, lm_loc=ll, nms_thresh=nms_thresh)
-            ids, slot, retired, tally = _launch(tr, dets, int(dets.size(-1)), B * slots, keep, None, B, slots, stream0, dry)
+        if thresh is None:
+            dets, _, keep = DC._run_batch(s, l, K, lm_heat=hm, lm_loc=ll, nms_thresh=nms_thresh)
+            ids, slot, retired, tally = _launch(tr, dets, int(dets.size(-1)), B * K, keep, None, B, K, stream0, dry)
             return dets, keep, ids, slot, retired, tally
-        slots, stream0 = kt[1], kt[3]
-        dets, keep, counts = EV._run_thresh_lists(s, l, kt[2], slots, hm, ll, nms_thresh)
+        slots = thresh[1]
+        dets, keep, counts = DC._run_thresh_batch(s, l, thresh[0], slots, hm, ll, nms_thresh, lists_behind_rows=False)
         ids, slot, retired, tally = _launch(tr, dets, int(dets.size(-1)), B * slots, keep, counts[2 * B:], B, slots, stream0, dry)
         return dets, keep, counts, ids, slot, retired, tally
     return eager
@@ -233,24 +221,14 @@ def _unpack(mode, res, dc):
     """per image (dets, keep, track_id, track_hits) from a chunk's results: host tensors where the flags above say so, device otherwise"""
     if mode == 'topk':
         d, k, ids = res[0].numpy(), res[1].numpy(), res[2].numpy()
-        out = []
-        for b in range(d.shape[0]):
-            n = int(k[b, 0])
-            out.append((d[b].copy(), [int(v) for v in k[b, 1:1 + n]], ids[0, b, :n].copy(), ids[1, b, :n].copy()))
-        return out
-    dets, keep, counts, ids = res[0], res[1], res[2].numpy().copy(), res[3].numpy()
-    B = (counts.shape[0] - 1) // 3
-    prefix = counts[2 * B:]
-    total = int(prefix[B])
-    rows = dets[:total].cpu().numpy().reshape(total, dc)             # the two copies whose sizes the counts decide
-    lists = keep[:total + B].cpu().numpy()
-    out = []
-    for b in range(B):
-        p, n = int(prefix[b]), int(counts[2 * b])
-        kl = lists[p + b:p + b + n + 1]
-        m = int(kl[0])
-        out.append((rows[p:p + n].copy(), [int(v) for v in kl[1:1 + m]], ids[0, b, :m].copy(), ids[1, b, :m].copy()))
-    return out
+        packed = [(d[b].copy(), _keep_list(k[b])) for b in range(d.shape[0])]
+    else:
+        dets, keep, counts, ids = res[0], res[1], res[2].numpy().copy(), res[3].numpy()
+        B = (counts.shape[0] - 1) // 3
+        total = int(counts[3 * B])
+        # the two copies whose sizes the counts decide
+        packed = DC._unpack_packed(counts[2 * B:], dets[:total].cpu().numpy(), keep[:total + B].cpu().numpy(), dc)
+    return [(d, kl, ids[0, b, :len(kl)].copy(), ids[1, b, :len(kl)].copy()) for b, (d, kl) in enumerate(packed)]
 
 
 def track_batch(net, images, *, tracker, stream0=0, K=10, score_thresh=None, max_dets=1024, nms_thresh=0.4, max_batch=32):
@@ -273,34 +251,22 @@ def track_batch(net, images, *, tracker, stream0=0, K=10, score_thresh=None, max
     (threshold; the rows and lists then come with two copies of exactly their size) to pinned memory.  Every chunk position owns an
     entry and the cache holds _MAX_GRAPHS = 8 per network, so keep streams / max_batch at or below that.  The capture's warm-up runs
     advance a scratch copy of the state.  Train mode and DBX_GRAPH=0 run the same launches eagerly."""
-    import os
-    from . import decode as DC
     fn = 'track_batch'
-    n = len(images) if isinstance(images, (list, tuple)) else int(DC._batch_of(images, 'images', fn).size(0))
-    _check_streams(fn, tracker, stream0, n)
+    _check_streams(fn, tracker, stream0, DC._frame_count(fn, images))
     tc = DC._thresh_or_topk(fn, K, score_thresh, max_dets)
     if tc is None and (not _integer(K) or not 1 <= K <= MAX_SLOTS):
         raise RuntimeError('%s: K=%r must be an integer in 1..%d' % (fn, K, MAX_SLOTS))
     if tc is not None and tc[1] > MAX_SLOTS:
         raise RuntimeError('%s: max_dets=%r must be an integer in 1..%d' % (fn, max_dets, MAX_SLOTS))
-    if isinstance(images, (list, tuple)):
-        shapes = {(tuple(im.shape[-3:]), im.dtype) for im in images if torch.is_tensor(im)}
-        if len(shapes) > 1:
-            raise RuntimeError('%s: the frames of a list must have one shape and dtype (stream j is image j), got %s'
-                               % (fn, sorted(str(s[0]) for s in shapes)))
+    DC._one_shape(fn, images, with_dtype=True)
     mode = ('topk', int(K)) if tc is None else ('thresh', tc[1], tc[0])
     flags = _TOPK_HOST if tc is None else _THRESH_HOST
-    graph = not net.training and os.environ.get('DBX_GRAPH', '1') != '0'
-    dc = 5 if net.KIND == 'DenseBox' else 13
+    dry, dc = DC._use_graph(net), DC._det_cols(net)
 
     def chunk(x, idx):
-        x = (x if x.is_cuda else x.cuda()).contiguous()
+        first = int(stream0) + idx[0]
         state, records = tracker._buffers(x.device)
-        kt = mode + (int(stream0) + idx[0], tracker.serial, state.data_ptr(), records.data_ptr()) + tracker.params()
-        eager = _track_eager(tracker, graph)
-        if graph:
-            res = DC._graph_replay(net, 'track', x, kt, nms_thresh, eager, to_host=flags)
-        else:
-            res = tuple(r.cpu() if f else r for r, f in zip(eager(net, x, kt, nms_thresh), flags))
+        key = (mode + (first, tracker.serial, state.data_ptr(), records.data_ptr()) + tracker.params(), float(nms_thresh))
+        res = DC._run_chunk(net, 'track', x, key, _track_eager(tracker, int(K), tc, first, nms_thresh, dry), flags)
         return _unpack(mode[0], res, dc)
     return DC._detect_many(fn, images, max_batch, chunk, with_index=True)
