@@ -80,6 +80,15 @@ class ShotRecord(C.Structure):
     _fields_ = [('stream', C.c_int32), ('slot', C.c_int32), ('shot', Shot)]
 
 
+class OverlayFrame(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('h', C.c_int32), ('w', C.c_int32)]
+
+
+class OverlayStyle(C.Structure):
+    _fields_ = [('box_color', C.c_uint8 * 4), ('text_color', C.c_uint8 * 4), ('mark_color', C.c_uint8 * 4), ('thickness', C.c_int32),
+                ('radius', C.c_int32), ('font_scale', C.c_int32), ('inset_scale', C.c_int32)]
+
+
 class ResizeJob(C.Structure):
     _fields_ = [('src', C.c_void_p), ('sh', C.c_int32), ('sw', C.c_int32), ('cx0', C.c_int32), ('cy0', C.c_int32),
                 ('cw', C.c_int32), ('ch', C.c_int32), ('pad_l', C.c_int32), ('pad_t', C.c_int32), ('pad_r', C.c_int32),
@@ -146,6 +155,10 @@ SIGNATURES = {
     'dbx_crop_sharpness': (C.c_int, [_VP, _I64, _I32, _I32, _I32, _VP, _VP]),
     'dbx_track_gallery_update': (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32,
                                            _I32, _I32, _I64, _I32, _D, _I32, _VP]),
+    'dbx_draw_overlay_batch': (C.c_int, [_VP, _I32, _I32, _I32, _I32, _VP, _I32, _I64, _VP, _VP, _I32, _VP, _VP, _VP, _I32, _I32,
+                                         C.POINTER(OverlayStyle), _VP]),
+    'dbx_overlay_font': (C.c_int, [_VP]),
+    'dbx_overlay_label': (C.c_int, [_D, _I32, C.c_char_p, _I32]),
     'dbx_resize_batch_workspace_bytes': (_I64, [_I32]),
     'dbx_resize_cubic_batch_u8': (C.c_int, [C.POINTER(ResizeJob), _I32, _I32, _VP, _VP, _VP]),
     'dbx_conv_wgrad_scratch_bytes': (_I64, [_I32, _PV, _PV, _I32, _I32]),

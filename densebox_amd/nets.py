@@ -173,6 +173,14 @@ class _DenseBoxBase(nn.Module):
         return track_plate_crops(self, images, tracker=tracker, gallery=gallery, stream0=stream0, K=K, nms_thresh=nms_thresh,
                                  max_batch=max_batch)
 
+    def annotate_batch(self, frames, *, tracker=None, stream0=0, inset=None, K=10, nms_thresh=0.4, max_batch=32, style=None):
+        """detect_batch() (track_batch() with a tracker) on uint8 frames, then the boxes, score labels, landmark discs and -- with
+        inset=(width, height) -- the rectified plates painted onto the frames on the device, in eval mode in one hipGraph per chunk: a
+        list of (dets, keep, track_id or None, annotated [H,W,3]) in input order (densebox_amd.viz.annotate_batch)."""
+        from .viz import annotate_batch
+        return annotate_batch(self, frames, tracker=tracker, stream0=stream0, inset=inset, K=K, nms_thresh=nms_thresh,
+                              max_batch=max_batch, style=style)
+
     def detect_batch_resized(self, images, size=720, K=10, nms_thresh=0.4, max_batch=32, score_thresh=None, max_dets=1024):
         """detect_batch() on uint8 frames of any sizes, each padded to a square and resized to size x size in one launch; a list of
         (dets, keep) in input order, coordinates mapped back to the source frames (densebox_amd.decode.detect_batch_resized)."""

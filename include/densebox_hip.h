@@ -64,7 +64,9 @@ const char* dbx_last_error(void);
  *      also at 13, without a bump: dbx_track, dbx_track_record, dbx_track_update_batch, dbx_track_append (multi-stream tracking by
  *      detection with its state on the device), pure additions likewise
  *      also at 13, without a bump: dbx_shot, dbx_shot_record, dbx_crop_sharpness, dbx_track_gallery_update (the best plate crop of
- *      every track kept on the device), pure additions likewise */
+ *      every track kept on the device), pure additions likewise
+ *      also at 13, without a bump: dbx_overlay_frame, dbx_overlay_style, dbx_draw_overlay_batch, dbx_overlay_font, dbx_overlay_label
+ *      (annotated frames painted on the device), pure additions likewise */
 #define DBX_ABI_VERSION 13
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
@@ -802,6 +804,73 @@ int dbx_track_gallery_update(const dbx_track* tracks, const int32_t* headers, co
                              dbx_shot* shots, uint8_t* shot_crops, dbx_shot_record* arena, uint8_t* arena_crops, int64_t* gstate,
                              int32_t batch, int32_t slots, int32_t streams, int32_t stream0, int32_t max_tracks, int32_t oh, int32_t ow,
                              int32_t c, int64_t capacity, int32_t policy, double min_score, int32_t commit, void* stream);
+
+/* ---- annotated frames (viz_result, DenseBox.py:3484-3560: cv2.rectangle, the filled label + cv2.putText, cv2.circle per landmark, the
+ * rectified plate shown next to the frame) painted on the device behind the decode, the plate crops and the tracking update ----
+ * The layout, default colours, thickness, radius and anchor points follow viz_result; the pixel semantics below are this project's own,
+ * restated in NumPy by tests/viz_ref.py.  OpenCV is not part of the reference tree: parity with cv2.rectangle / putText / circle is
+ * unpinned.
+ * dbx_draw_overlay_batch: ONE launch, a workgroup of 256 threads per 128 x 16 tile of a frame on a grid of (the tiles of a max_h x
+ * max_w frame, batch); it copies nothing from the host and never synchronises, so it can be captured into a hipGraph behind the decode,
+ * dbx_plate_crops_batch and dbx_track_update_batch.
+ * frames: a DEVICE table of `batch` records; frame b is an interleaved uint8 [h][w][c] image of any size up to max_h x max_w, read at
+ * src and written at dst.  dst == src draws in place; any other overlap is the caller's error.  dets / det_cols / det_rows / keep /
+ * prefix / slots: the description dbx_match_gt_batch and dbx_track_update_batch take (prefix == NULL: slot layout; otherwise the packed
+ * layout of dbx_detect_thresh_batch).  track_id: int32 [batch][slots] by list position, as dbx_track_update_batch writes it, or NULL.
+ * crops uint8 [batch][slots][oh][ow][c] and ok int32 [batch][slots], by list position, as dbx_plate_crops_batch writes them with sel =
+ * keep; both NULL: no inset.
+ * Notation: I(v) = v + 0.5 in float64, truncated toward zero; T(v) = v truncated toward zero; a value is usable when it is finite and
+ * |v| < 2^30.
+ * Everything is clipped to the frame.  Within a frame the kept rows are painted in list order, later over earlier; within a row the
+ * order is outline, label background, label text, discs 0..3, inset; a pixel nothing covers is src's.  So every dst pixel is a function
+ * of the inputs alone, not of scheduling.  A row whose x1, y1, x2, y2 (columns 0..3) are not all usable paints nothing.  X1 = I(x1), Y1,
+ * X2, Y2 likewise; L, R = min, max(X1, X2); Tp, Bt = min, max(Y1, Y2); t = thickness, a = t / 2 (integer), b = t - a.
+ *   outline  (box colour) L-a <= x <= R+a, Tp-a <= y <= Bt+a, except the pixels with L+b <= x <= R-b and Tp+b <= y <= Bt-b.
+ *   label    when font_scale = s > 0: the text has n characters of a 6 x 8 cell, tw = 6 s n, th = 8 s.  Background (box colour):
+ *            X1 <= x <= X1+tw+3, Y1-th-5 <= y <= Y1 (viz_result's pt_1 .. pt_1 + (w + 3, -h - 5)).  Text (text colour): a set font
+ *            pixel (i, j) of character m covers the s x s block at x = X1 + 2 + (6 m + i) s, y = Y1 - 2 - th + j s.
+ *   discs    (mark colour) when det_cols == 13 and radius = r >= 0: for q = 0..3 the centre is (T(row[5+2q]), T(row[6+2q])), both
+ *            usable, else that disc is skipped; it covers dx*dx + dy*dy <= r*r.
+ *   inset    when crops is given and ok[b][j] != 0 (j the list position): with m = inset_scale, px = L-a and py = Bt+a+2, the pixel
+ *            (x, y) in [px, px + ow m) x [py, py + oh m) takes crops[b][j][(y-py)/m][(x-px)/m].
+ * Text: "#", the id in decimal and a space when track_id is given and track_id[b][j] >= 0; then the score v = row[4]: when v is finite
+ * and |v| < 1000, exactly what C's "%.3f" prints (the exact binary value correctly rounded, ties to even, "-" whenever the sign bit is
+ * set: "-0.000"), computed in integer arithmetic on the double's bits; otherwise "---".  The characters are "0123456789.-# ".
+ * Channel ch of a painted pixel takes color[ch] of its colour.
+ * Device data is never trusted as a bound: keep counts are clamped to min(rows of the frame, slots), a keep entry outside the frame's
+ * rows paints nothing, a frame with a bad prefix pair has no rows and is copied undrawn; a frame record with a null src or dst, a
+ * non-positive size, h > max_h or w > max_w is skipped and its dst not written.  For every other frame the call writes every byte of
+ * dst (in place: every byte that changes) and nothing outside it.  A tile no row meets is moved with 16-byte accesses where src and dst
+ * allow the same ones, bytes at the ragged ends.  LDS: 88 bytes per slot; there is no scratch buffer.
+ * Refused with DBX_ERR_ARG before anything is queued: batch < 0, c outside 1..4, max_h or max_w < 1, det_cols not 5 or 13, slots
+ * outside 1..1024, det_rows < 0 (or below batch * slots in slot layout), thickness outside 1..16, radius outside -1..32, font_scale
+ * outside 0..8, inset_scale outside 1..8, exactly one of crops / ok null, crops with ow or oh < 1, a null frames / dets / keep / style,
+ * more than 2^24 - 1 tiles or 65535 frames (one grid).  batch == 0: no-op.
+ * dbx_overlay_frame is 24 bytes (src 0, dst 8, h 16, w 20); dbx_overlay_style is 28 bytes (the three colours at 0, 4, 8, then thickness,
+ * radius, font_scale, inset_scale from 12).
+ *
+ * The same text and font code compiled for the host (no GPU needed):
+ * dbx_overlay_font: out uint8 [14][8], row j of glyph g of "0123456789.-# " in out[g][j], bit i = column i (5 x 7 in the 6 x 8 cell).
+ * dbx_overlay_label: the label of (score, track_id; a negative id: none) as a NUL-terminated string in out; returns its length (at
+ * most 21), or DBX_ERR_ARG when out is null or out_len < 22. */
+typedef struct dbx_overlay_frame {
+    const uint8_t* src;    /* device image [h][w][c] */
+    uint8_t* dst;          /* device image [h][w][c]; may equal src */
+    int32_t h, w;
+} dbx_overlay_frame;
+typedef struct dbx_overlay_style {
+    uint8_t box_color[4], text_color[4], mark_color[4];    /* channel ch of a pixel takes color[ch] */
+    int32_t thickness;     /* 1..16 */
+    int32_t radius;        /* -1 (no discs) .. 32 */
+    int32_t font_scale;    /* 0 (no label) .. 8 */
+    int32_t inset_scale;   /* 1..8 */
+} dbx_overlay_style;
+int dbx_draw_overlay_batch(const dbx_overlay_frame* frames, int32_t batch, int32_t c, int32_t max_h, int32_t max_w,
+                           const double* dets, int32_t det_cols, int64_t det_rows, const int32_t* keep, const int32_t* prefix,
+                           int32_t slots, const int32_t* track_id, const uint8_t* crops, const int32_t* ok, int32_t ow, int32_t oh,
+                           const dbx_overlay_style* style, void* stream);
+int dbx_overlay_font(uint8_t* out);
+int dbx_overlay_label(double score, int32_t track_id, char* out, int32_t out_len);
 
 /* ---- batched pad + bicubic resize (pad_img + cv2.resize(..., INTER_CUBIC), DenseBox.py:1282-1340; the patch cutters' resize of a
  * cropped window) ----
