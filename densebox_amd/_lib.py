@@ -95,6 +95,24 @@ class ResizeJob(C.Structure):
                 ('pad_b', C.c_int32), ('pad_value', C.c_int32), ('dh', C.c_int32), ('dw', C.c_int32), ('dst_off', C.c_int64)]
 
 
+class PatchJob(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('scale_x', C.c_double), ('scale_y', C.c_double), ('row_bytes', C.c_int32),
+                ('cx0', C.c_int32), ('cy0', C.c_int32), ('cw', C.c_int32), ('ch', C.c_int32), ('pad_l', C.c_int32), ('pad_t', C.c_int32),
+                ('vw', C.c_int32), ('vh', C.c_int32), ('dh', C.c_int32), ('dw', C.c_int32), ('pad_value', C.c_int32),
+                ('tiles_x', C.c_int32), ('frame', C.c_int32), ('kind', C.c_int32), ('reserved', C.c_int32)]
+
+
+class PatchGeom(C.Structure):
+    _fields_ = [('status', C.c_int32), ('x0', C.c_int32), ('y0', C.c_int32), ('x1', C.c_int32), ('y1', C.c_int32),
+                ('labels', C.c_int32 * 12), ('reserved', C.c_int32)]
+
+
+class PatchPlanIO(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in (
+        'frames', 'plates', 'plate0', 'cand', 'draws', 'state', 'jobs', 'labels', 'bbox', 'vertices', 'label', 'count', 'tally',
+        'status', 'slot', 'cand_out', 'draws_out')]
+
+
 class MergeXform(C.Structure):
     _fields_ = [('scale', C.c_double), ('off_x', C.c_double), ('off_y', C.c_double)]
 
@@ -161,6 +179,11 @@ SIGNATURES = {
     'dbx_overlay_label': (C.c_int, [_D, _I32, C.c_char_p, _I32]),
     'dbx_resize_batch_workspace_bytes': (_I64, [_I32]),
     'dbx_resize_cubic_batch_u8': (C.c_int, [C.POINTER(ResizeJob), _I32, _I32, _VP, _VP, _VP]),
+    'dbx_patch_plan': (C.c_int, [C.POINTER(PatchPlanIO), _I32, _I32, _I32, _I32, _I32, _D, _D, _I32, _VP]),
+    'dbx_patch_cut': (C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP]),
+    'dbx_patch_plan_host': (C.c_int, [_I32, _I32, _I32, _VP, _I32, _D, _D, _D, _I32, C.POINTER(PatchGeom)]),
+    'dbx_patch_draw': (C.c_int, [_I64, _I64, _I32, _I32, _VP]),
+    'dbx_patch_check_tables': (C.c_int, [_VP, _I32, _VP, _I32, _VP, _I32]),
     'dbx_conv_wgrad_scratch_bytes': (_I64, [_I32, _PV, _PV, _I32, _I32]),
     'dbx_conv_wgrad': (C.c_int, [_I32, _PV, _PV, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _I32, _VP]),
     'dbx_conv_wgrad_slice': (C.c_int, [_I32, _PV, _PV, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP]),

@@ -6,10 +6,14 @@ Normalize (DenseBox.py:766-772).  Here: the three label parsers (host string wor
 constructors) and the device-side transform, which is fused into the layout kernel -- pass uint8 ``[N,H,W,3]`` tensors to
 ``net.forward`` (``dbx_u8hwc_to_framed``).  JPEG decoding / directory walking stay out of scope.
 """
+import ctypes as C
 import re
 
 import numpy as np
 import torch
+
+from . import _lib
+from .rectify import host_images, to_device
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)   # DenseBox.py:770
 IMAGENET_STD = (0.229, 0.224, 0.225)    # DenseBox.py:771
@@ -52,3 +56,189 @@ def collate_labels(names):
     """File names -> (bbox[N,4], vertices[N,8], labels[N,1]) float32 tensors, DenseBoxDataset semantics + default collate."""
     b, v, l = zip(*[parse_densebox_label(n) for n in names])
     return torch.from_numpy(np.stack(b)), torch.from_numpy(np.stack(v)), torch.from_numpy(np.stack(l))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Training patches sampled and cut on the device (dbx_patch_plan + dbx_patch_cut; include/densebox_hip.h, "training patch
+# sampling"): the reference's gen_pos_patch and the negative path of gen_pure_neg_patches (process_plate.py:167-352, :711-749).
+PATCH_SIDE = 240
+MAX_CANDIDATES = 4096
+PATCH_STATUS = ('accepted', 'landmark rule', 'degenerate', 'empty slice', 'vertex outside its frame', 'negative: no 240 x 240 window',
+                'negative: overlaps a plate', 'accepted beyond the capacity')
+
+
+def plate_tables(plates, n_frames):
+    """plates: one list per frame of plates, a plate being 8 integers (4 (x, y) vertices in annotation order) or 4 pairs; or an int
+    [P, 9] array of (frame, 8 integers) rows sorted by frame.  Returns the host tables (plates int32 [P, 9], plate0 int32
+    [n_frames + 1]) of dbx_patch_plan, checked by dbx_patch_check_tables."""
+    if isinstance(plates, np.ndarray) or torch.is_tensor(plates):
+        rows = np.ascontiguousarray(plates.cpu().numpy() if torch.is_tensor(plates) else plates)
+        if rows.ndim != 2 or rows.shape[1] != 9 or rows.dtype.kind not in 'iu':
+            raise RuntimeError('plate_tables: a plate table must be an integer [P, 9] array, got %s %s' % (rows.dtype, list(rows.shape)))
+        rows = rows.astype(np.int32)
+    else:
+        if len(plates) != n_frames:
+            raise RuntimeError('plate_tables: %d lists of plates for %d frames' % (len(plates), n_frames))
+        flat = []
+        for f, ps in enumerate(plates):
+            for p in ps:
+                v = np.asarray(p).reshape(-1)
+                if v.size != 8 or np.any(v != np.floor(v)):
+                    raise RuntimeError('plate_tables: a plate must be 8 integers (4 (x, y) vertices), got %r in frame %d' % (p, f))
+                flat.append([f] + [int(x) for x in v])
+        rows = np.asarray(flat, dtype=np.int32).reshape(-1, 9)
+    frames_of = rows[:, 0].astype(np.int64)
+    plate0 = np.searchsorted(frames_of, np.arange(n_frames + 1), side='left').astype(np.int32)
+    _lib.check(_lib.lib().dbx_patch_check_tables(rows.ctypes.data_as(C.c_void_p) if len(rows) else None, len(rows),
+                                                 plate0.ctypes.data_as(C.c_void_p), n_frames, None, 0))
+    return rows, plate0
+
+
+class PatchPlan(object):
+    """The device tensors one dbx_patch_plan launch writes: jobs (uint8 [n, 96], dbx_patch_job records), labels_i32 int32 [n, 12],
+    bbox float32 [n, 4], vertices [n, 8], labels [n, 1], count int32 [1], tally int32 [8], status / slot int32 [M], cand int32 [M, 2],
+    draws float64 [M, 2].  Rows at or past count are not written (the tensors start zeroed)."""
+
+    def __init__(self, M, n, device):
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+        self.M, self.n = int(M), int(n)
+        self.jobs = z((n, 96), torch.uint8)
+        self.labels_i32, self.bbox, self.vertices, self.labels = z((n, 12), torch.int32), z((n, 4), torch.float32), \
+            z((n, 8), torch.float32), z((n, 1), torch.float32)
+        self.count, self.tally = z((1,), torch.int32), z((8,), torch.int32)
+        self.status, self.slot = z((max(M, 1),), torch.int32)[:M], z((max(M, 1),), torch.int32)[:M]
+        self.cand, self.draws = z((max(M, 1), 2), torch.int32)[:M], z((max(M, 1), 2), torch.float64)[:M]
+
+
+def plan_patches(table, n_frames, c, plates, plate0, M, n, cand=None, draws=None, state=None, neg_frac=0.1, offset_radius=15, th=0,
+                 out=None):
+    """The dbx_patch_plan launch alone, on the current stream; nothing is copied and nothing waits.  table: rectify.frame_table's
+    device table; plates int32 [P, 9] / plate0 int32 [n_frames + 1]: device tensors (plate_tables, uploaded); cand int32 [M, 2] +
+    draws float64 [M, 2] (injected mode) or state int64 [2] = (seed, counter) (device mode), device tensors.  Returns the PatchPlan
+    (`out`, or a new one)."""
+    out = out if out is not None else PatchPlan(M, n, table.device)
+    io = _lib.PatchPlanIO()
+    io.frames, io.plates, io.plate0 = table.data_ptr(), (plates.data_ptr() if plates.numel() else None), plate0.data_ptr()
+    io.cand = cand.data_ptr() if cand is not None else None
+    io.draws = draws.data_ptr() if draws is not None else None
+    io.state = state.data_ptr() if state is not None else None
+    io.jobs, io.labels, io.bbox, io.vertices, io.label = out.jobs.data_ptr(), out.labels_i32.data_ptr(), out.bbox.data_ptr(), \
+        out.vertices.data_ptr(), out.labels.data_ptr()
+    io.count, io.tally = out.count.data_ptr(), out.tally.data_ptr()
+    if M:
+        io.status, io.slot, io.cand_out, io.draws_out = out.status.data_ptr(), out.slot.data_ptr(), out.cand.data_ptr(), out.draws.data_ptr()
+    _lib.check(_lib.lib().dbx_patch_plan(C.byref(io), int(n_frames), int(plates.numel() // 9), int(c), int(M), int(n), float(neg_frac),
+                                         float(offset_radius), int(th), _lib.stream_ptr()))
+    return out
+
+
+def cut_patches(plan, c, patches=None):
+    """The dbx_patch_cut launch alone: the plan's first `count` jobs into `patches` (uint8 [n, 240, 240, c], any byte alignment; a new
+    zeroed tensor when None).  Slots at or past the count keep what they held."""
+    if patches is None:
+        patches = torch.zeros((plan.n, PATCH_SIDE, PATCH_SIDE, c), dtype=torch.uint8, device=plan.jobs.device)
+    if patches.dtype != torch.uint8 or tuple(patches.shape) != (plan.n, PATCH_SIDE, PATCH_SIDE, c) or not patches.is_contiguous():
+        raise RuntimeError('cut_patches: patches must be a contiguous uint8 [%d, 240, 240, %d] tensor, got %s %s'
+                           % (plan.n, c, patches.dtype, list(patches.shape)))
+    _lib.check(_lib.lib().dbx_patch_cut(C.c_void_p(plan.jobs.data_ptr()), C.c_void_p(plan.count.data_ptr()), plan.n, int(c),
+                                        C.c_void_p(patches.data_ptr()), _lib.stream_ptr()))
+    return patches
+
+
+def _upload(*arrays):
+    """The int32 / float64 host arrays as views of ONE uploaded buffer (each at an 8-byte boundary)."""
+    offs, pos = [], 0
+    for a in arrays:
+        offs.append(pos)
+        pos += (a.nbytes + 7) // 8 * 8
+    host = np.zeros(max(pos, 8), np.uint8)
+    for a, o in zip(arrays, offs):
+        host[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    dev = torch.from_numpy(host).cuda()
+    return [dev[o:o + a.nbytes].view(torch.from_numpy(a).dtype).view(a.shape) for a, o in zip(arrays, offs)]
+
+
+def _frame_records(dev):
+    rec = (_lib.CropFrame * len(dev))()
+    for r, im in zip(rec, dev):
+        r.src, r.sh, r.sw = im.data_ptr(), int(im.size(0)), int(im.size(1))
+    return np.frombuffer(rec, dtype=np.uint8).copy()
+
+
+def sample_patches(frames, plates, n, candidates=None, draws=None, neg_frac=0.1, offset_radius=15, seed=0, counter=0, m=None, th=0):
+    """One upload + the two launches.  frames: as for resize.pad_resize_batch (host or device images of any sizes, C = 1..4);
+    plates: as for plate_tables; n: the capacity.  Injected mode: candidates int [M, 2] = (kind, index) with draws float64 [M, 2];
+    device mode (candidates None): m candidates (default ceil(1.5 n)) from the hash of (seed, counter).  Returns (patches uint8
+    [n, 240, 240, C], plan): plan.count patches are valid, plan.bbox / vertices / labels are net.loss's inputs."""
+    host, _ = host_images('sample_patches', frames, None)
+    dev = to_device(frames, host)
+    c = int(dev[0].size(2))
+    rows, plate0 = plate_tables(plates, len(dev))
+    if (candidates is None) != (draws is None):
+        raise RuntimeError('sample_patches: candidates and draws go together (injected mode), or neither (device mode)')
+    parts = [_frame_records(dev), rows, plate0]
+    if candidates is not None:
+        cand = np.ascontiguousarray(np.asarray(candidates, dtype=np.int32).reshape(-1, 2))
+        dr = np.ascontiguousarray(np.asarray(draws, dtype=np.float64).reshape(-1, 2))
+        if len(cand) != len(dr):
+            raise RuntimeError('sample_patches: %d candidates but %d rows of draws' % (len(cand), len(dr)))
+        M = len(cand)
+        _lib.check(_lib.lib().dbx_patch_check_tables(rows.ctypes.data_as(C.c_void_p) if len(rows) else None, len(rows),
+                                                     plate0.ctypes.data_as(C.c_void_p), len(dev), cand.ctypes.data_as(C.c_void_p), M))
+        parts += [cand, dr]
+    else:
+        M = int(m) if m is not None else min(MAX_CANDIDATES, (3 * int(n) + 1) // 2)
+        parts += [np.array([seed, counter], dtype=np.int64)]
+    up = _upload(*parts)
+    table, d_rows, d_plate0 = up[0], up[1], up[2]
+    if candidates is not None:
+        plan = plan_patches(table, len(dev), c, d_rows, d_plate0, M, n, cand=up[3], draws=up[4], neg_frac=neg_frac,
+                            offset_radius=offset_radius, th=th)
+    else:
+        plan = plan_patches(table, len(dev), c, d_rows, d_plate0, M, n, state=up[3], neg_frac=neg_frac, offset_radius=offset_radius, th=th)
+    patches = cut_patches(plan, c)
+    plan.keep = (dev, up)              # the table holds raw addresses: the frames live as long as the plan
+    return patches, plan
+
+
+class PatchSampler(object):
+    """Fresh training patches every step with frames, tables, state and outputs resident on the device.  frames / plates: as for
+    sample_patches; n: patches per batch; every batch decides ceil(oversample * n) candidates (at most 4096), of which a fraction
+    neg_frac are pure negatives.  next_batch() is the two launches plus a 4-byte read of the count."""
+
+    def __init__(self, frames, plates, n, oversample=1.5, neg_frac=0.1, seed=0, offset_radius=15, th=0, allow_short=False):
+        if int(n) < 1 or not oversample >= 1.0:
+            raise RuntimeError('PatchSampler: n=%r must be positive and oversample=%r at least 1' % (n, oversample))
+        host, _ = host_images('PatchSampler', frames, None)
+        self.frames = to_device(frames, host)
+        self.c, self.n = int(self.frames[0].size(2)), int(n)
+        self.M = min(MAX_CANDIDATES, int(np.ceil(float(oversample) * self.n)))
+        rows, plate0 = plate_tables(plates, len(self.frames))
+        self.table, self.plates, self.plate0, self.state = _upload(_frame_records(self.frames), rows, plate0,
+                                                                   np.array([seed, 0], dtype=np.int64))
+        self.neg_frac, self.offset_radius, self.th, self.allow_short = float(neg_frac), offset_radius, int(th), bool(allow_short)
+        self.plan = PatchPlan(self.M, self.n, self.table.device)
+        self.patches = torch.zeros((self.n, PATCH_SIDE, PATCH_SIDE, self.c), dtype=torch.uint8, device=self.table.device)
+        self.totals = torch.zeros(8, dtype=torch.int64, device=self.table.device)
+
+    def launch(self):
+        """The two launches (and the tally's accumulation) on the current stream, without any read: what a graph capture holds."""
+        plan_patches(self.table, len(self.frames), self.c, self.plates, self.plate0, self.M, self.n, state=self.state,
+                     neg_frac=self.neg_frac, offset_radius=self.offset_radius, th=self.th, out=self.plan)
+        cut_patches(self.plan, self.c, self.patches)
+        self.totals += self.plan.tally
+
+    def next_batch(self, allow_short=None):
+        """(patches uint8 [n, 240, 240, C], bbox [n, 4], vertices [n, 8], labels [n, 1], count): net.forward's and net.loss's inputs.
+        The tensors are the sampler's own and are overwritten by the next call.  Raises when fewer than n candidates were accepted,
+        unless allow_short (here or at construction; then the first `count` rows are the batch: slice them)."""
+        self.launch()
+        count = int(self.plan.count.item())
+        if count < self.n and not (self.allow_short if allow_short is None else allow_short):
+            raise RuntimeError('PatchSampler: %d of %d candidates were accepted, fewer than n=%d; raise oversample (status tally: %s)'
+                               % (count, self.M, self.n, self.plan.tally.tolist()))
+        return self.patches, self.plan.bbox, self.plan.vertices, self.plan.labels, count
+
+    def status_tally(self):
+        """{status name: candidates so far}, summed over every batch."""
+        return dict(zip(PATCH_STATUS, self.totals.tolist()))

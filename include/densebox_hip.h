@@ -66,7 +66,9 @@ const char* dbx_last_error(void);
  *      also at 13, without a bump: dbx_shot, dbx_shot_record, dbx_crop_sharpness, dbx_track_gallery_update (the best plate crop of
  *      every track kept on the device), pure additions likewise
  *      also at 13, without a bump: dbx_overlay_frame, dbx_overlay_style, dbx_draw_overlay_batch, dbx_overlay_font, dbx_overlay_label
- *      (annotated frames painted on the device), pure additions likewise */
+ *      (annotated frames painted on the device), pure additions likewise
+ *      also at 13, without a bump: dbx_patch_job, dbx_patch_geom, dbx_patch_plan_io, dbx_patch_plan, dbx_patch_cut, dbx_patch_plan_host,
+ *      dbx_patch_draw, dbx_patch_check_tables (training patches sampled and cut on the device), pure additions likewise */
 #define DBX_ABI_VERSION 13
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
@@ -903,6 +905,124 @@ typedef struct dbx_resize_job {
 } dbx_resize_job;
 int64_t dbx_resize_batch_workspace_bytes(int32_t njobs);
 int dbx_resize_cubic_batch_u8(const dbx_resize_job* jobs, int32_t njobs, int32_t c, uint8_t* dst, void* workspace, void* stream);
+
+/* ---- training patch sampling (gen_pos_patch, process_plate.py:167-352, with format_4_vertices :109 and bbox_from_vertices :1247; the
+ * negative path of gen_pure_neg_patches :711-749 with intersect_small :639-666) ----
+ * Two launches and no host read between them: dbx_patch_plan (ONE workgroup) decides M candidates, gives the accepted ones their
+ * output slots in candidate order and writes a job record + a label row per slot; dbx_patch_cut (n * 60 workgroups, fixed by n alone)
+ * runs the batched resize's tile body on those records into patches uint8 [n][240][240][c].  Both can be captured into a hipGraph.
+ *
+ * Tables (device): frames = n_frames dbx_crop_frame records; plates int32 [n_plates][9] = (frame, x0, y0, x1, y1, x2, y2, x3, y3), the
+ * four vertices in annotation order, rows sorted by frame; plate0 int32 [n_frames + 1], plate0[f] .. plate0[f + 1] the rows of frame f.
+ *
+ * Candidate i is (kind, index, d0, d1): kind 0 = positive (index: a plates row; d0, d1: the two uniform(-1, 1) values), kind 1 =
+ * negative (index: a frame; d0, d1: the integer centre x, y as doubles).
+ *   injected mode (io->cand and io->draws both non-NULL): read from cand int32 [M][2] and draws float64 [M][2].
+ *   device mode (both NULL): made from the hash h(seed, counter, i, j) of draw number j = 0..3 below, k = h >> 11 (53 bits):
+ *     j = 0  kind: negative when k * 2^-53 < neg_frac (with n_plates == 0 every candidate is negative, with neg_frac == 0 none is)
+ *     j = 1  index: k mod n_plates (positive) or k mod n_frames (negative)
+ *     j = 2, 3  positive: d = -1.0 + 2.0 * (k * 2^-53), the value set of Python's random.uniform(-1, 1);
+ *               negative: d0 = 120 + k mod (W - 240), d1 = 120 + k mod (H - 240) of the drawn frame (0, 0 when status 5)
+ *     state = device int64 [2] = (seed, counter); the launch's last act is counter += 1, so a replay of a captured launch draws anew.
+ *   Both modes write the candidates they used to cand_out / draws_out.
+ * The hash (unsigned 64-bit arithmetic, wrapping):
+ *     mix(x):  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31
+ *     h = mix(mix(seed + 0x9E3779B97F4A7C15 * (counter + 1)) + 0xD1B54A32D192ED03 * (i + 1) + 0x8CB92BA72F3D8DD7 * (j + 1))
+ *
+ * Geometry of a positive in a W x H frame (float64, the reference's order of operations, no contraction; I(x) = (int)(x + 0.5),
+ * truncation toward zero, saturated to +-10^9 where Python would go on):
+ *   status 4 when the frame record has a null src, a non-positive size or more than 2^31 - 1 bytes, or a vertex has x outside
+ *     0 .. W - 1 or y outside 0 .. H - 1 -- refused before any geometry (the reference would go on with negative slice indices).
+ *   d0 or d1 not finite (|d| > 10^100, injected mode only): status 2.
+ *   format_4_vertices: a STABLE sort of the four on x; the first two are the left pair, the others IN ANNOTATION ORDER the right pair
+ *     (membership by value); of each pair the first in a stable sort on y is "up".  Any two vertices equal by value make the reference
+ *     raise IndexError: status 2.
+ *   bbox = (min(lu.x, ld.x), max(ru.x, rd.x), min(lu.y, ru.y), max(ld.y, rd.y)); cx = I((x_min + x_max) * 0.5), cy alike;
+ *   pw = 4.0 * (x_max - x_min), ph alike; org = (cx - pw * 0.5 - d0 * offset_radius, cy - ph * 0.5 - d1 * offset_radius);
+ *   end = org + (pw, ph); then :208-222: if org.x < 0 or org.y < 0: each negative org becomes 0 and pw, ph = end - org; if
+ *   end.x >= W or end.y >= H: end.x = W - 1 where end.x >= W, end.y = H - 1 where end.y >= H, and pw, ph = end - org.
+ *   pw == 0 or ph == 0 (ZeroDivisionError in the reference): status 2.
+ *   label = I(((v - org) / (pw, ph)) * 240.0) for bbox left-up, bbox right-down, lu, ru, rd, ld: the 12 integers of the file name.
+ *   The rule :274-277, literally, with the SOURCE frame's W and H: rejected (status 1) when lu.x < 8 or lu.y < 8 or ru.x > W - 8 or
+ *     ru.y < 8 or rd.x > W - 8 or rd.y > H - 8 or ld.x < 8 or ld.y > H - 8.
+ *   slice = I(org) : I(end) on both axes; x1 <= x0 or y1 <= y0: status 3 (the reference returns an empty patch).  A patch that passes
+ *     the rule has end > 0, so no index is negative and the slice is the window as it stands.
+ * A negative in frame f: status 4 for an unusable frame record; status 5 when W < 241 or H < 241 or (injected) the centre is not an
+ * integer pair with 120 <= cx < W - 120, 120 <= cy < H - 120; status 2 when ANY plate of the frame has two equal vertices (every plate is
+ * formatted before the test runs); then intersect_small over the frame's plates in order, with a plate's sorted lu, rd:
+ * iw = min(rd.x, cx + 120) - max(lu.x, cx - 120), ih alike; iw < 0 or ih < 0: accepted at once; iw * ih > th: status 6; all plates passed (or none): accepted.  The window is [cx - 120, cx + 120) x [cy - 120,
+ * cy + 120) at scale 1, which the 11-bit coefficients make an exact copy; the label row is all zero.
+ * An index outside its table (which dbx_patch_check_tables refuses on the host) is never followed: status 2.
+ *
+ * status: 0 accepted, 1 landmark rule, 2 degenerate, 3 empty slice, 4 vertex outside its frame, 5 negative: no 240 x 240 window,
+ * 6 negative: overlaps a plate, 7 accepted but beyond the capacity n.
+ * Slots: an exclusive scan of the accept flags in candidate order; slot[i] = that rank for an accepted candidate (status 0: < n, status 7:
+ * >= n), -1 otherwise.  count = min(accepted, n).  Slot s < count gets jobs[s], labels[s] (int32 [12]; all zero for a negative), bbox[s] =
+ * labels[s][0..3] / 4, vertices[s] = labels[s][4..11] / 4 and label[s] = 1 (0 for a negative) as float32 -- what DenseBoxDataset reads
+ * from the file name.  Rows at or past count are not written.  tally[k] = candidates with status k.
+ * dbx_patch_job (96 bytes, the resize kernel's device record): src 0, dst 8 (unused: 0), scale_x 16, scale_y 24 (cw / 240.0, ch / 240.0),
+ * row_bytes 32 (sw * c), cx0 36, cy0 40, cw 44, ch 48, pad_l 52, pad_t 56 (0), vw 60, vh 64 (= cw, ch), dh 68, dw 72 (240), pad_value 76
+ * (0), tiles_x 80 (4), frame 84, kind 88, reserved 92. */
+#define DBX_PATCH_SIDE 240
+#define DBX_PATCH_MAX_CAND 4096
+#define DBX_PATCH_NSTATUS 8
+typedef struct dbx_patch_job {
+    const uint8_t* src;
+    uint8_t* dst;
+    double scale_x, scale_y;
+    int32_t row_bytes;
+    int32_t cx0, cy0, cw, ch, pad_l, pad_t, vw, vh, dh, dw, pad_value, tiles_x;
+    int32_t frame, kind, reserved;
+} dbx_patch_job;
+/* one candidate's geometry (72 bytes): status 0, x0 4, y0 8, x1 12, y1 16 (the slice; zeros unless status is 0 or 3), labels 20, reserved 68 */
+typedef struct dbx_patch_geom {
+    int32_t status;
+    int32_t x0, y0, x1, y1;
+    int32_t labels[12];
+    int32_t reserved;
+} dbx_patch_geom;
+/* device pointers of dbx_patch_plan (136 bytes: 17 pointers in this order) */
+typedef struct dbx_patch_plan_io {
+    const dbx_crop_frame* frames;
+    const int32_t* plates;       /* [n_plates][9]; may be NULL when n_plates == 0 */
+    const int32_t* plate0;       /* [n_frames + 1] */
+    const int32_t* cand;         /* [M][2] (kind, index), or NULL: device mode */
+    const double* draws;         /* [M][2], or NULL: device mode */
+    int64_t* state;              /* [2] (seed, counter); needed in device mode only */
+    dbx_patch_job* jobs;         /* [n] */
+    int32_t* labels;             /* [n][12] */
+    float* bbox;                 /* [n][4] */
+    float* vertices;             /* [n][8] */
+    float* label;                /* [n][1] */
+    int32_t* count;              /* [1] */
+    int32_t* tally;              /* [DBX_PATCH_NSTATUS] */
+    int32_t* status;             /* [M] */
+    int32_t* slot;               /* [M] */
+    int32_t* cand_out;           /* [M][2] */
+    double* draws_out;           /* [M][2] */
+} dbx_patch_plan_io;
+/* Refused with DBX_ERR_ARG before anything is queued: a null io or a null pointer in it (cand and draws: both or neither; state may be NULL
+ * in injected mode; plates may be NULL when n_plates == 0; status, slot, cand_out, draws_out may be NULL when M == 0), n_frames < 1,
+ * n_plates < 0, c outside 1..4, M outside 0..4096, n < 1, neg_frac not in [0, 1], offset_radius not finite or negative, th < 0.
+ * M == 0: count = 0, a zero tally, and (device mode) the counter still advances. */
+int dbx_patch_plan(const dbx_patch_plan_io* io, int32_t n_frames, int32_t n_plates, int32_t c, int32_t M, int32_t n, double neg_frac,
+                   double offset_radius, int32_t th, void* stream);
+/* jobs / count as dbx_patch_plan left them; patches device uint8 [n][240][240][c] at any byte alignment.  Slot s < min(count, n) is bit for
+ * bit dbx_resize_cubic_batch_u8 of its window to 240 x 240; slots at or past count are not written.  Refused: a null pointer, n < 1 or
+ * above 2^24 / 60, c outside 1..4. */
+int dbx_patch_cut(const dbx_patch_job* jobs, const int32_t* count, int32_t n, int32_t c, uint8_t* patches, void* stream);
+/* The plan's geometry of ONE candidate on the host (the same __host__ __device__ function the kernel runs), for a CPU check.  kind 0:
+ * verts = the plate's 8 integers, n_verts = 1; kind 1: verts = the 8 integers of each of the frame's n_verts plates.  Refused: a null
+ * pointer, kind outside 0..1, n_verts < 0 (or != 1 for kind 0), W or H < 1, th < 0. */
+int dbx_patch_plan_host(int32_t kind, int32_t W, int32_t H, const int32_t* verts, int32_t n_verts, double d0, double d1,
+                        double offset_radius, int32_t th, dbx_patch_geom* out);
+/* out[(r * 4 + j)] = h(seed, counter, i0 + r, j) for r < count, j < 4 (the raw 64-bit hash).  Refused: a null out, count < 0, i0 < 0. */
+int dbx_patch_draw(int64_t seed, int64_t counter, int32_t i0, int32_t count, uint64_t* out);
+/* Host check of host copies of the tables, to be run before they are uploaded.  Refused with DBX_ERR_ARG: a null plate0, n_frames < 1,
+ * n_plates < 0, a plates row whose frame is outside 0 .. n_frames - 1 or below the row before it (not sorted by frame), a plate0 that is
+ * not the row prefix of those frames, and -- when cand is not NULL -- M outside 0..4096, a kind outside 0..1, a positive's index outside
+ * 0 .. n_plates - 1, a negative's index outside 0 .. n_frames - 1. */
+int dbx_patch_check_tables(const int32_t* plates, int32_t n_plates, const int32_t* plate0, int32_t n_frames, const int32_t* cand, int32_t M);
 
 /* ---- data-parallel gradient exchange (new capability; the reference is single-GPU) ----
  * One process per GPU.  Rank 0 makes a 128-byte id (dbx_dp_unique_id) and hands it to the other ranks by any host channel;
