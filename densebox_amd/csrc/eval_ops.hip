@@ -3,36 +3,14 @@
 // so floating-point contraction is OFF in this file: `area_d + area_g - w * h` rounds the product before the subtraction.
 #pragma clang fp contract(off)
 #include "common.hpp"
+#include "det_frame.hpp"
 
 #include <cmath>
 
+#define EVAL_MAX_SLOTS 4096
 #define EVAL_MATCH_THREADS 256
 #define EVAL_APPEND_THREADS 1024
 #define EVAL_NO_CLAIM 0x7fffffff
-
-// Where frame b's rows and keep list are, from device data that is never trusted as a bound: r0 the frame's first row of dets, n its rows,
-// kl its keep list (the count, then row numbers within the frame), k the clamped count.  Slot layout (prefix == NULL): dbx_detect_batch's;
-// packed layout: dbx_detect_thresh_batch's, a frame whose prefix pair is negative, decreasing or ends beyond det_rows is empty (and its
-// list is not read).
-struct EvalFrame { long long r0, n; const int* kl; int k; };
-__device__ static inline EvalFrame eval_frame(const int* keep, const int* prefix, int b, int slots, long long det_rows) {
-    EvalFrame f;
-    if (prefix) {
-        const long long p0 = prefix[b], p1 = prefix[b + 1];
-        const bool ok = p0 >= 0 && p1 >= p0 && p1 <= det_rows;
-        f.r0 = ok ? p0 : 0;
-        f.n = ok ? p1 - p0 : 0;
-        f.kl = keep + (ok ? p0 + b : 0);
-    } else {
-        f.r0 = (long long)b * slots;
-        f.n = slots;
-        f.kl = keep + (long long)b * (slots + 1);
-    }
-    const long long lim = f.n < slots ? f.n : slots;
-    const int c = lim > 0 ? f.kl[0] : 0;
-    f.k = c < 0 ? 0 : (c > lim ? (int)lim : c);
-    return f;
-}
 
 struct MatchArgs {
     const double* dets; const int* keep; const int* prefix;
@@ -73,7 +51,7 @@ __global__ __launch_bounds__(EVAL_MATCH_THREADS) void match_gt_batch_kernel(cons
     }
     if (ngt) atomicAdd(&cnt[3], ngt);
     __syncthreads();
-    const EvalFrame f = eval_frame(a.keep, a.prefix, b, a.slots, a.det_rows);
+    const DetFrame f = det_frame(a.keep, a.prefix, b, a.slots, a.det_rows);
     const int dc = a.det_cols;
     const double nan = __builtin_nan("");
     for (int i = tid; i < a.slots; i += nt) {
@@ -139,22 +117,11 @@ __global__ __launch_bounds__(EVAL_MATCH_THREADS) void match_gt_batch_kernel(cons
 
 static size_t match_lds_bytes(int max_gt) { return ((size_t)max_gt * (5 * 8 + 4 + 1) + 15) & ~(size_t)15; }
 
-// the description of the rows and lists that both entry points take
-static int eval_check_rows(const char* fn, int32_t det_cols, int64_t det_rows, const int32_t* prefix, int32_t batch, int32_t slots) {
-    DBX_REQUIRE(batch >= 0, "%s: batch=%d is negative", fn, batch);
-    DBX_REQUIRE(det_cols == 5 || det_cols == 13, "%s: det_cols=%d must be 5 or 13", fn, det_cols);
-    DBX_REQUIRE(slots >= 1 && slots <= 4096, "%s: slots=%d must be 1..4096", fn, slots);
-    DBX_REQUIRE(det_rows >= 0, "%s: det_rows=%lld is negative", fn, (long long)det_rows);
-    DBX_REQUIRE(prefix || det_rows >= (int64_t)batch * slots, "%s: det_rows=%lld is below batch * slots = %lld", fn, (long long)det_rows,
-                (long long)batch * slots);
-    return DBX_OK;
-}
-
 extern "C" int dbx_match_gt_batch(const double* dets, int32_t det_cols, int64_t det_rows, const int32_t* keep, const int32_t* prefix,
                                   int32_t batch, int32_t slots, const double* gt, int32_t gt_cols, const int32_t* gt_counts,
                                   const uint8_t* gt_ignore, int32_t max_gt, double iou_thresh, int32_t* status, int32_t* gt_index,
                                   double* iou, double* lm_err, int32_t* tally, void* stream) {
-    const int rc = eval_check_rows("match_gt_batch", det_cols, det_rows, prefix, batch, slots);
+    const int rc = det_rows_check("match_gt_batch", det_cols, det_rows, prefix, batch, slots, EVAL_MAX_SLOTS);
     if (rc != DBX_OK) return rc;
     DBX_REQUIRE(gt_cols == 4 || gt_cols == 12, "match_gt_batch: gt_cols=%d must be 4 or 12", gt_cols);
     DBX_REQUIRE(max_gt >= 1 && max_gt <= 1024, "match_gt_batch: max_gt=%d must be 1..1024", max_gt);
@@ -202,7 +169,7 @@ __global__ __launch_bounds__(EVAL_APPEND_THREADS) void eval_append_kernel(const 
         if (t[i]) atomicAdd(&sums[i], t[i]);
     const double nan = __builtin_nan("");
     for (int b = 0; b < a.batch; ++b) {
-        const EvalFrame f = eval_frame(a.keep, a.prefix, b, a.slots, a.det_rows);
+        const DetFrame f = det_frame(a.keep, a.prefix, b, a.slots, a.det_rows);
         for (int c0 = 0; c0 < f.k; c0 += EVAL_APPEND_THREADS) {
             const int i = c0 + tid;
             const size_t o = (size_t)b * a.slots + i;
@@ -244,7 +211,7 @@ extern "C" int dbx_eval_append(const double* dets, int32_t det_cols, int64_t det
                                int32_t batch, int32_t slots, const int32_t* status, const double* lm_err, const int32_t* tally,
                                dbx_eval_record* records, int64_t capacity, int64_t* state, void* stream) {
     static_assert(sizeof(dbx_eval_record) == 24, "dbx_eval_record is 24 bytes");
-    const int rc = eval_check_rows("eval_append", det_cols, det_rows, prefix, batch, slots);
+    const int rc = det_rows_check("eval_append", det_cols, det_rows, prefix, batch, slots, EVAL_MAX_SLOTS);
     if (rc != DBX_OK) return rc;
     DBX_REQUIRE(capacity >= 0, "eval_append: capacity=%lld is negative", (long long)capacity);
     if (batch == 0) return DBX_OK;

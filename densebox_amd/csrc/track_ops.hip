@@ -61,7 +61,7 @@ __global__ __launch_bounds__(TRACK_MAX_TRACKS) void track_update_batch_kernel(co
 
     if (tid < 2) cnt[tid] = 0;
     __syncthreads();
-    const TrackFrame fr = track_frame(a.keep, a.prefix, b, S, a.det_rows);
+    const DetFrame fr = det_frame(a.keep, a.prefix, b, S, a.det_rows);
     int counted = 0;
     for (int i = tid; i < fr.k; i += nt) {
         const int r = fr.kl[1 + i];
@@ -219,18 +219,14 @@ extern "C" int dbx_track_update_batch(const double* dets, int32_t det_cols, int6
                                       void* stream) {
     static_assert(sizeof(dbx_track) == 104, "dbx_track is 104 bytes");
     const char* fn = "track_update_batch";
-    DBX_REQUIRE(batch >= 0, "%s: batch=%d is negative", fn, batch);
+    const int rc = det_rows_check(fn, det_cols, det_rows, prefix, batch, slots, TRACK_MAX_SLOTS);
+    if (rc != DBX_OK) return rc;
     DBX_REQUIRE(stream0 >= 0 && streams >= 0 && (int64_t)stream0 + batch <= streams, "%s: streams %d..%lld are not all in 0..%d", fn, stream0,
                 (long long)stream0 + batch - 1, streams - 1);
-    DBX_REQUIRE(det_cols == 5 || det_cols == 13, "%s: det_cols=%d must be 5 or 13", fn, det_cols);
-    DBX_REQUIRE(slots >= 1 && slots <= TRACK_MAX_SLOTS, "%s: slots=%d must be 1..%d", fn, slots, TRACK_MAX_SLOTS);
     DBX_REQUIRE(max_tracks >= 1 && max_tracks <= TRACK_MAX_TRACKS, "%s: max_tracks=%d must be 1..%d", fn, max_tracks, TRACK_MAX_TRACKS);
     DBX_REQUIRE(max_age >= 0, "%s: max_age=%d is negative", fn, max_age);
     DBX_REQUIRE(!std::isnan(iou_thresh) && !std::isnan(alpha) && !std::isnan(beta) && !std::isnan(birth_score),
                 "%s: iou_thresh, alpha, beta and birth_score must not be NaN", fn);
-    DBX_REQUIRE(det_rows >= 0, "%s: det_rows=%lld is negative", fn, (long long)det_rows);
-    DBX_REQUIRE(prefix || det_rows >= (int64_t)batch * slots, "%s: det_rows=%lld is below batch * slots = %lld", fn, (long long)det_rows,
-                (long long)batch * slots);
     if (batch == 0) return DBX_OK;
     DBX_REQUIRE(dets && keep && headers && tracks && track_id && track_slot && track_hits && retired && tally, "%s: null argument", fn);
     TrackArgs a;

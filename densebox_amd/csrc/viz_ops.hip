@@ -226,7 +226,7 @@ __global__ __launch_bounds__(VIZ_THREADS) void draw_overlay_batch_kernel(const V
     unsigned cbox, ctext, cmark;                                   // colour[ch] in byte ch
     __builtin_memcpy(&cbox, a.st.box_color, 4); __builtin_memcpy(&ctext, a.st.text_color, 4); __builtin_memcpy(&cmark, a.st.mark_color, 4);
 
-    const TrackFrame fr = track_frame(a.keep, a.prefix, b, a.slots, a.det_rows);
+    const DetFrame fr = det_frame(a.keep, a.prefix, b, a.slots, a.det_rows);
     int cnt = 0;
     for (int c0 = 0; c0 < fr.k; c0 += VIZ_THREADS) {
         const int i = c0 + tid;
@@ -285,14 +285,10 @@ extern "C" int dbx_draw_overlay_batch(const dbx_overlay_frame* frames, int32_t b
     static_assert(sizeof(dbx_overlay_frame) == 24 && sizeof(dbx_overlay_style) == 28, "dbx_overlay_frame is 24 bytes, dbx_overlay_style 28");
     static_assert(sizeof(VizEnt) == 88, "a collected row is 88 bytes of LDS");
     const char* fn = "draw_overlay_batch";
-    DBX_REQUIRE(batch >= 0, "%s: batch=%d is negative", fn, batch);
+    const int rc = det_rows_check(fn, det_cols, det_rows, prefix, batch, slots, VIZ_MAX_SLOTS);
+    if (rc != DBX_OK) return rc;
     DBX_REQUIRE(c >= 1 && c <= 4, "%s: c=%d must be 1..4", fn, c);
     DBX_REQUIRE(max_h >= 1 && max_w >= 1, "%s: max_h=%d and max_w=%d must be positive", fn, max_h, max_w);
-    DBX_REQUIRE(det_cols == 5 || det_cols == 13, "%s: det_cols=%d must be 5 or 13", fn, det_cols);
-    DBX_REQUIRE(slots >= 1 && slots <= VIZ_MAX_SLOTS, "%s: slots=%d must be 1..%d", fn, slots, VIZ_MAX_SLOTS);
-    DBX_REQUIRE(det_rows >= 0, "%s: det_rows=%lld is negative", fn, (long long)det_rows);
-    DBX_REQUIRE(prefix || det_rows >= (int64_t)batch * slots, "%s: det_rows=%lld is below batch * slots = %lld", fn, (long long)det_rows,
-                (long long)batch * slots);
     DBX_REQUIRE(style, "%s: null style", fn);
     DBX_REQUIRE(style->thickness >= 1 && style->thickness <= 16, "%s: thickness=%d must be 1..16", fn, style->thickness);
     DBX_REQUIRE(style->radius >= -1 && style->radius <= 32, "%s: radius=%d must be -1..32", fn, style->radius);

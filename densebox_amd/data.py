@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .rectify import host_images, to_device
+from .rectify import frame_records, host_images, to_device
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)   # DenseBox.py:770
 IMAGENET_STD = (0.229, 0.224, 0.225)    # DenseBox.py:771
@@ -158,13 +158,6 @@ def _upload(*arrays):
     return [dev[o:o + a.nbytes].view(torch.from_numpy(a).dtype).view(a.shape) for a, o in zip(arrays, offs)]
 
 
-def _frame_records(dev):
-    rec = (_lib.CropFrame * len(dev))()
-    for r, im in zip(rec, dev):
-        r.src, r.sh, r.sw = im.data_ptr(), int(im.size(0)), int(im.size(1))
-    return np.frombuffer(rec, dtype=np.uint8).copy()
-
-
 def sample_patches(frames, plates, n, candidates=None, draws=None, neg_frac=0.1, offset_radius=15, seed=0, counter=0, m=None, th=0):
     """One upload + the two launches.  frames: as for resize.pad_resize_batch (host or device images of any sizes, C = 1..4);
     plates: as for plate_tables; n: the capacity.  Injected mode: candidates int [M, 2] = (kind, index) with draws float64 [M, 2];
@@ -176,7 +169,7 @@ def sample_patches(frames, plates, n, candidates=None, draws=None, neg_frac=0.1,
     rows, plate0 = plate_tables(plates, len(dev))
     if (candidates is None) != (draws is None):
         raise RuntimeError('sample_patches: candidates and draws go together (injected mode), or neither (device mode)')
-    parts = [_frame_records(dev), rows, plate0]
+    parts = [np.frombuffer(frame_records(dev), dtype=np.uint8), rows, plate0]
     if candidates is not None:
         cand = np.ascontiguousarray(np.asarray(candidates, dtype=np.int32).reshape(-1, 2))
         dr = np.ascontiguousarray(np.asarray(draws, dtype=np.float64).reshape(-1, 2))
@@ -214,7 +207,7 @@ class PatchSampler(object):
         self.c, self.n = int(self.frames[0].size(2)), int(n)
         self.M = min(MAX_CANDIDATES, int(np.ceil(float(oversample) * self.n)))
         rows, plate0 = plate_tables(plates, len(self.frames))
-        self.table, self.plates, self.plate0, self.state = _upload(_frame_records(self.frames), rows, plate0,
+        self.table, self.plates, self.plate0, self.state = _upload(np.frombuffer(frame_records(self.frames), dtype=np.uint8), rows, plate0,
                                                                    np.array([seed, 0], dtype=np.int64))
         self.neg_frac, self.offset_radius, self.th, self.allow_short = float(neg_frac), offset_radius, int(th), bool(allow_short)
         self.plan = PatchPlan(self.M, self.n, self.table.device)

@@ -15,7 +15,7 @@ import itertools
 import numpy as np
 import torch
 
-from . import _lib, decode as DC
+from . import _lib, decode as DC, rows as R
 from ._lib import check, ptr, stream_ptr
 from .decode import _host, _integer
 
@@ -120,20 +120,19 @@ def _pack_gt(frames, max_gt, gt_cols):
 
 
 # ------------------------------------------------------------------------------------------------------------ the launches
-def _launch_match(dets, dc, det_rows, keep, prefix, B, slots, gtbuf, gt_cols, max_gt, iou_thresh):
-    """dbx_match_gt_batch on device tensors, the ground truth in a device buffer of _gt_layout: (status, gt_index int32 [B, slots], iou,
-    lm_err (or None) float64 [B, slots], tally int32 [B, 5]) device tensors"""
-    dev = dets.device
+def _launch_match(rows, gtbuf, gt_cols, max_gt, iou_thresh):
+    """dbx_match_gt_batch on the device rows `rows` (rows.Rows), the ground truth in a device buffer of _gt_layout: (status, gt_index
+    int32 [B, slots], iou, lm_err (or None) float64 [B, slots], tally int32 [B, 5]) device tensors"""
+    dev, B, slots = rows.dets.device, rows.B, rows.slots
     o_cnt, o_ign, _ = _gt_layout(B, max_gt, gt_cols)
     status = torch.empty((B, slots), dtype=torch.int32, device=dev)
     index = torch.empty((B, slots), dtype=torch.int32, device=dev)
     iou = torch.empty((B, slots), dtype=torch.float64, device=dev)
-    err = torch.empty((B, slots), dtype=torch.float64, device=dev) if (dc == 13 and gt_cols == 12) else None
+    err = torch.empty((B, slots), dtype=torch.float64, device=dev) if (rows.dc == 13 and gt_cols == 12) else None
     tally = torch.empty((B, 5), dtype=torch.int32, device=dev)
     g = gtbuf.data_ptr()
-    check(_lib.lib().dbx_match_gt_batch(ptr(dets), dc, det_rows, ptr(keep), ptr(prefix), B, slots, C.c_void_p(g), gt_cols,
-                                        C.c_void_p(g + o_cnt), C.c_void_p(g + o_ign), max_gt, float(iou_thresh), ptr(status), ptr(index),
-                                        ptr(iou), ptr(err), ptr(tally), stream_ptr()))
+    check(_lib.lib().dbx_match_gt_batch(*rows.args(), C.c_void_p(g), gt_cols, C.c_void_p(g + o_cnt), C.c_void_p(g + o_ign), max_gt,
+                                        float(iou_thresh), ptr(status), ptr(index), ptr(iou), ptr(err), ptr(tally), stream_ptr()))
     return status, index, iou, err, tally
 
 
@@ -148,40 +147,22 @@ def match_batch(dets, keeps, gt_boxes, gt_ignore=None, gt_quads=None, iou_thresh
     Returns, per image, (status int32 [k], gt_index int32 [k], iou float64 [k], lm_err float64 [k] or None) for the k entries of its keep
     list in order (the module docstring has the semantics)."""
     fn = 'match_batch'
-    if not isinstance(dets, (list, tuple)) or not isinstance(keeps, (list, tuple)) or len(dets) != len(keeps) or not dets:
-        raise RuntimeError('%s: dets and keeps must be non-empty lists with one entry per image' % fn)
+    p = R.pack_host(fn, dets, keeps, max_slots=MAX_SLOTS)
     if isinstance(iou_thresh, bool) or not isinstance(iou_thresh, (int, float, np.integer, np.floating)) or np.isnan(iou_thresh):
         raise RuntimeError('%s: iou_thresh=%r must be a number' % (fn, iou_thresh))
-    B = len(dets)
+    B, slots, lists = p.B, p.slots, p.lists
     frames = _gt_frames(fn, B, gt_boxes, gt_ignore, gt_quads, MAX_GT)
-    rows = [_host(d).astype(np.float64) for d in dets]
-    dcs = {r.shape[1] for r in rows if r.ndim == 2}
-    if any(r.ndim != 2 for r in rows) or len(dcs) != 1 or not dcs <= {5, 13}:
-        raise RuntimeError('%s: every dets entry must be [n, 5] or [n, 13], all alike; got %s' % (fn, [list(r.shape) for r in rows]))
-    dc = dcs.pop()
-    if gt_quads is not None and dc != 13:
-        raise RuntimeError('%s: gt_quads need 13-column rows (DenseBoxLM / DenseBoxLMLOC), got %d columns' % (fn, dc))
-    lists = [np.asarray(k, np.int64).reshape(-1) for k in keeps]
-    for i, (r, k) in enumerate(zip(rows, lists)):
-        if k.size and (k.min() < 0 or k.max() >= r.shape[0]):
-            raise RuntimeError('%s: keeps[%d] names a row outside 0..%d' % (fn, i, r.shape[0] - 1))
-    slots = max(1, max(max(r.shape[0], k.size) for r, k in zip(rows, lists)))
-    if slots > MAX_SLOTS:
-        raise RuntimeError('%s: %d rows in one image exceed %d' % (fn, slots, MAX_SLOTS))
+    if gt_quads is not None and p.dc != 13:
+        raise RuntimeError('%s: gt_quads need 13-column rows (DenseBoxLM / DenseBoxLMLOC), got %d columns' % (fn, p.dc))
     max_gt = max(1, max(f[0].shape[0] for f in frames))
     gt_cols = 12 if gt_quads is not None else 4
     gt = _pack_gt(frames, max_gt, gt_cols)
-    nd, nk = B * slots * dc * 8, (B * (slots + 1) * 4 + 7) // 8 * 8
-    host = np.zeros(nd + nk + gt.size, np.uint8)
-    hd, hk = host[:nd].view(np.float64).reshape(B, slots, dc), host[nd:nd + B * (slots + 1) * 4].view(np.int32).reshape(B, slots + 1)
-    for i, (r, k) in enumerate(zip(rows, lists)):
-        hd[i, :r.shape[0]] = r
-        hk[i, 0] = k.size
-        hk[i, 1:1 + k.size] = k
-    host[nd + nk:] = gt
+    o_gt = p.nd + (p.nk + 7) // 8 * 8                                                  # the ground truth behind the lists, 8-byte padded
+    host = np.zeros(o_gt + gt.size, np.uint8)
+    p.write(host, 0, p.nd)
+    host[o_gt:] = gt
     buf = torch.from_numpy(host).cuda()                                               # the one upload
-    d_dets, d_keep = buf[:nd].view(torch.float64), buf[nd:nd + B * (slots + 1) * 4].view(torch.int32)
-    status, index, iou, err, _ = _launch_match(d_dets, dc, B * slots, d_keep, None, B, slots, buf[nd + nk:], gt_cols, max_gt, iou_thresh)
+    status, index, iou, err, _ = _launch_match(p.on(buf, 0, p.nd), buf[o_gt:], gt_cols, max_gt, iou_thresh)
     parts = [status.view(torch.uint8).reshape(-1), index.view(torch.uint8).reshape(-1), iou.view(torch.uint8).reshape(-1)]
     if err is not None:
         parts.append(err.view(torch.uint8).reshape(-1))
@@ -254,11 +235,6 @@ class Evaluator:
 
 
 # ------------------------------------------------------------------------------------------------------------ net.evaluate_batch
-def _run_thresh_lists(score_map, loc_map, score_thresh, max_dets, lm_heat, lm_loc, nms_thresh):
-    """decode._run_thresh_batch with the keep lists in a buffer of their own (the kernel tests of the matcher and the tracker feed on it)"""
-    return DC._run_thresh_batch(score_map, loc_map, score_thresh, max_dets, lm_heat, lm_loc, nms_thresh, lists_behind_rows=False)
-
-
 def _eval_eager(ev, gtbuf, gt_cols, K, thresh, nms_thresh, dry_outside_capture):
     """The eager function of evaluate_batch's chunks: forward, decode (+ NMS), dbx_match_gt_batch, dbx_eval_append.  thresh: None for
     the top-K decode of K rows, or (score_thresh, max_dets).  Under _graph_replay the function also runs twice as a warm-up before the
@@ -267,21 +243,13 @@ def _eval_eager(ev, gtbuf, gt_cols, K, thresh, nms_thresh, dry_outside_capture):
     def eager(net, images):
         s, l, hm, ll = DC._forward_maps(net, images)
         B = int(images.size(0))
-        if thresh is None:
-            slots, prefix = K, None
-            dets, _, keep = DC._run_batch(s, l, slots, lm_heat=hm, lm_loc=ll, nms_thresh=nms_thresh)
-        else:
-            slots = thresh[1]
-            dets, keep, counts = DC._run_thresh_batch(s, l, thresh[0], slots, hm, ll, nms_thresh, lists_behind_rows=False)
-            prefix = counts[2 * B:]
-        dc = int(dets.size(-1))
-        status, index, iou, err, tally = _launch_match(dets, dc, B * slots, keep, prefix, B, slots, gtbuf, gt_cols, ev.max_gt, ev.iou_thresh)
+        rows, _ = R.decode_rows(s, l, hm, ll, B, K, thresh, nms_thresh)
+        status, index, iou, err, tally = _launch_match(rows, gtbuf, gt_cols, ev.max_gt, ev.iou_thresh)
         records, state = ev._buffers(images.device)
         dry = dry_outside_capture and not torch.cuda.is_current_stream_capturing()
-        check(_lib.lib().dbx_eval_append(ptr(dets), dc, B * slots, ptr(keep), ptr(prefix), B, slots, ptr(status), ptr(err), ptr(tally),
-                                         None if dry else ptr(records), 0 if dry else ev.capacity, ptr(ev._dry if dry else state),
-                                         stream_ptr()))
-        return tally, (dets, keep, prefix, status, index, iou, err, records, state, gtbuf)
+        check(_lib.lib().dbx_eval_append(*rows.args(), ptr(status), ptr(err), ptr(tally), None if dry else ptr(records),
+                                         0 if dry else ev.capacity, ptr(ev._dry if dry else state), stream_ptr()))
+        return tally, (rows.dets, rows.keep, rows.prefix, status, index, iou, err, records, state, gtbuf)
     return eager
 
 
@@ -305,8 +273,8 @@ def evaluate_batch(net, images, gt_boxes, *, evaluator, K=10, score_thresh=None,
     if not isinstance(evaluator, Evaluator):
         raise RuntimeError('%s: evaluator must be an evaluate.Evaluator, got %s' % (fn, type(evaluator).__name__))
     tc = DC._thresh_or_topk(fn, K, score_thresh, max_dets)
-    if tc is None and (not _integer(K) or not 1 <= K <= MAX_SLOTS):
-        raise RuntimeError('%s: K=%r must be an integer in 1..%d' % (fn, K, MAX_SLOTS))
+    if tc is None:
+        R._check_K(fn, K, MAX_SLOTS)
     if gt_quads is not None:
         DC._require_landmarks(fn, net, 'compare gt_quads with')
     frames = _gt_frames(fn, DC._frame_count(fn, images), gt_boxes, gt_ignore, gt_quads, evaluator.max_gt)

@@ -8,9 +8,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, decode as DC, track as TR
+from . import _lib, decode as DC, rows as R, track as TR
 from ._lib import check, ptr, stream_ptr
-from .decode import _host, _integer
+from .decode import _integer
 
 MAX_PIXELS = 16384           # oh * ow of a crop: its luma plane is staged in LDS as 16-bit values
 POLICIES = {'sharpness': 0, 'score': 1}
@@ -157,39 +157,6 @@ def sharpness(crops):
     return out if t.is_cuda else out.cpu()
 
 
-# ------------------------------------------------------------------------------------------------------------ the launches
-def _launch(tr, gal, dets, dc, det_rows, keep, B, slots, stream0, crops, ok, dry=False):
-    """dbx_track_update_batch, dbx_track_gallery_update and dbx_track_append on device tensors, for streams stream0 .. stream0 + B - 1:
-    track._launch with the gallery between its two launches.  crops uint8 [B, slots, oh, ow, c] and ok int32 [B, slots] are what
-    dbx_plate_crops_batch wrote with sel = keep.  dry: the tracker's launches advance a scratch copy of its state and append nothing,
-    and the gallery's reads it and writes nothing (commit = 0).  Returns what track._launch returns."""
-    dev = dets.device
-    state, records = tr._buffers(dev)
-    live, arena, gstate = gal._buffers(dev)
-    if dry:
-        tr._dry.copy_(state)
-        state = tr._dry
-    o_tab, o_app, _ = tr._layout()
-    base = state.data_ptr()
-    ids = torch.empty((2, B, slots), dtype=torch.int32, device=dev)
-    slot = torch.empty((B, slots), dtype=torch.int32, device=dev)
-    retired = torch.empty(B * tr.max_tracks * TR.TRACK.itemsize, dtype=torch.uint8, device=dev)
-    tally = torch.empty((B, 6), dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    check(L.dbx_track_update_batch(ptr(dets), dc, det_rows, ptr(keep), None, B, slots, C.c_void_p(base), C.c_void_p(base + o_tab),
-                                   tr.streams, stream0, tr.max_tracks, tr.iou_thresh, tr.max_age, tr.alpha, tr.beta, tr.birth_score,
-                                   ptr(ids[0]), ptr(slot), ptr(ids[1]), ptr(retired), ptr(tally), stream_ptr()))
-    n = tr.streams * tr.max_tracks
-    check(L.dbx_track_gallery_update(C.c_void_p(base + o_tab), C.c_void_p(base), ptr(slot), ptr(crops), ptr(ok), ptr(retired), ptr(tally),
-                                     C.c_void_p(base + o_app), ptr(live), C.c_void_p(live.data_ptr() + n * SHOT.itemsize), ptr(arena),
-                                     C.c_void_p(arena.data_ptr() + gal.capacity * SHOT_RECORD.itemsize), ptr(gstate), B, slots,
-                                     tr.streams, stream0, tr.max_tracks, gal.oh, gal.ow, gal.channels, gal.capacity,
-                                     POLICIES[gal.policy], gal.min_score, 0 if dry else 1, stream_ptr()))
-    check(L.dbx_track_append(ptr(retired), ptr(tally), B, tr.max_tracks, stream0, None if dry else ptr(records), 0 if dry else tr.capacity,
-                             C.c_void_p(base + o_app), stream_ptr()))
-    return ids, slot, retired, tally
-
-
 def update_batch(images, dets, keeps, *, tracker, gallery, stream0=0):
     """The host results of any detect_* call with landmarks tracked and their best shots kept: track.update_batch with the crops and the
     gallery in between.  Entry j is the next frame of stream stream0 + j.
@@ -203,48 +170,27 @@ def update_batch(images, dets, keeps, *, tracker, gallery, stream0=0):
     int32 [k]) for the k entries of its keep list."""
     from . import rectify
     fn = 'gallery.update_batch'
-    if not isinstance(dets, (list, tuple)) or not isinstance(keeps, (list, tuple)) or len(dets) != len(keeps) or not dets:
-        raise RuntimeError('%s: dets and keeps must be non-empty lists with one entry per image' % fn)
-    B = len(dets)
-    TR._check_streams(fn, tracker, stream0, B)
+    p = R.pack_host(fn, dets, keeps, cols=(13,), max_slots=TR.MAX_SLOTS)
+    TR._check_streams(fn, tracker, stream0, p.B)
     _check_gallery(fn, gallery, tracker)
     host_ims, _ = rectify.host_images(fn, images, gallery.channels)
-    if len(host_ims) != B:
-        raise RuntimeError('%s: %d images for %d entries of dets' % (fn, len(host_ims), B))
-    rows = [_host(d).astype(np.float64) for d in dets]
-    if any(r.ndim != 2 or r.shape[1] != 13 for r in rows):
-        raise RuntimeError('%s: every dets entry must be [n, 13] (rows with landmarks); got %s' % (fn, [list(r.shape) for r in rows]))
-    lists = [np.asarray(k, np.int64).reshape(-1) for k in keeps]
-    for i, (r, k) in enumerate(zip(rows, lists)):
-        if k.size and (k.min() < 0 or k.max() >= r.shape[0]):
-            raise RuntimeError('%s: keeps[%d] names a row outside 0..%d' % (fn, i, r.shape[0] - 1))
-    slots = max(1, max(max(r.shape[0], k.size) for r, k in zip(rows, lists)))
-    if slots > TR.MAX_SLOTS:
-        raise RuntimeError('%s: %d rows in one image exceed %d' % (fn, slots, TR.MAX_SLOTS))
-    nd = B * slots * 13 * 8
-    host = np.zeros(nd + B * (slots + 1) * 4, np.uint8)
-    hd, hk = host[:nd].view(np.float64).reshape(B, slots, 13), host[nd:].view(np.int32).reshape(B, slots + 1)
-    for i, (r, k) in enumerate(zip(rows, lists)):
-        hd[i, :r.shape[0]] = r
-        hk[i, 0] = k.size
-        hk[i, 1:1 + k.size] = k
+    if len(host_ims) != p.B:
+        raise RuntimeError('%s: %d images for %d entries of dets' % (fn, len(host_ims), p.B))
     dev_ims = rectify.to_device(images, host_ims)
     dev = tracker._buffers(dev_ims[0].device)[0].device
     dev_ims = [im.to(dev) for im in dev_ims]
-    buf = torch.from_numpy(host).to(dev)                                              # the one upload of rows and lists
-    d_dets, d_keep = buf[:nd].view(torch.float64), buf[nd:].view(torch.int32)
+    rows = p.upload(dev)                                                               # the one upload of rows and lists
     table = rectify.frame_table(dev_ims)
-    crops, ok = rectify._crops_launch(table, B, gallery.channels, d_dets.data_ptr() + 5 * 8, 13, slots * 13, d_keep, slots, gallery.ow,
-                                      gallery.oh, dev)
-    ids, _, _, _ = _launch(tracker, gallery, d_dets, 13, B * slots, d_keep, B, slots, int(stream0), crops, ok)
-    h = ids.cpu().numpy()                                                              # the one copy back
-    return [(h[0, i, :k.size].copy(), h[1, i, :k.size].copy()) for i, k in enumerate(lists)]
+    crops, ok = rectify._crops_launch(table, p.B, gallery.channels, rows.dets.data_ptr() + 5 * 8, 13, p.slots * 13, rows.keep, p.slots,
+                                      gallery.ow, gallery.oh, dev)
+    h = TR._launch(tracker, rows, int(stream0), gallery=(gallery, crops, ok))[0].cpu().numpy()      # the one copy back
+    return [(h[0, i, :k.size].copy(), h[1, i, :k.size].copy()) for i, k in enumerate(p.lists)]
 
 
 # ------------------------------------------------------------------------------------------------------------ net.track_plate_crops
 def _eager(tr, gal, K, stream0, nms_thresh, dry_outside_capture):
     """The eager function of track_plate_crops' chunks, for the streams from stream0 on: forward, dbx_detect_batch,
-    dbx_plate_crops_batch, then the three launches of _launch.  The frame table is uploaded on the first call for a tensor (a warm-up
+    dbx_plate_crops_batch, then the three launches of track._launch.  The frame table is uploaded on the first call for a tensor (a warm-up
     run, outside the capture) and reused for the same address afterwards, as in detect_plate_crops.  Under _graph_replay the warm-up
     runs are dry.  Returns the tensors that go to the host first, then every other tensor the launches wrote or read: a graph entry
     keeps them all."""
@@ -252,9 +198,8 @@ def _eager(tr, gal, K, stream0, nms_thresh, dry_outside_capture):
 
     def eager(net, images):
         dets, keep, crops, ok, table = crops_eager(net, images)
-        B, dc = int(dets.size(0)), int(dets.size(2))
         dry = dry_outside_capture and not torch.cuda.is_current_stream_capturing()
-        ids, slot, retired, tally = _launch(tr, gal, dets, dc, B * K, keep, B, K, stream0, crops, ok, dry)
+        ids, slot, retired, tally = TR._launch(tr, R.Rows(dets, keep, None, int(dets.size(0)), K), stream0, dry, (gal, crops, ok))
         return dets, keep, ids, slot, retired, tally, crops, ok, table
     return eager
 
@@ -293,15 +238,12 @@ def track_plate_crops(net, images, *, tracker, gallery, stream0=0, K=10, nms_thr
     _check_gallery(fn, gallery, tracker)
     if gallery.channels != 3:
         raise RuntimeError('%s: the gallery has %d channels, the frames 3' % (fn, gallery.channels))
-    if not _integer(K) or not 1 <= K <= TR.MAX_SLOTS:
-        raise RuntimeError('%s: K=%r must be an integer in 1..%d' % (fn, K, TR.MAX_SLOTS))
+    R._check_K(fn, K, TR.MAX_SLOTS)
     dry = DC._use_graph(net)
 
     def chunk(x, idx):
         first = int(stream0) + idx[0]
-        state, records = tracker._buffers(x.device)
-        key = ((int(K), first, tracker.serial, state.data_ptr(), records.data_ptr()) + tracker.params() + gallery._key(x.device),
-               float(nms_thresh))
+        key = ((int(K),) + tracker._key(x.device, first) + gallery._key(x.device), float(nms_thresh))
         res = DC._run_chunk(net, fn, x, key, _eager(tracker, gallery, int(K), first, nms_thresh, dry), _HOST)
         return TR._unpack('topk', res, 13)
     return DC._detect_many(fn, images, max_batch, chunk, with_index=True)

@@ -230,13 +230,18 @@ def plate_rectangle(size):
     return [[0, 0], [w - 1, 0], [w - 1, h - 1], [0, h - 1]]
 
 
-def frame_table(dev):
-    """The device table of dbx_crop_frame records {src, sh, sw} of contiguous uint8 [H,W,C] CUDA tensors (one small upload).  It holds
-    raw addresses: keep `dev` alive while the table is in use."""
+def frame_records(dev):
+    """The ctypes array of dbx_crop_frame records {src, sh, sw} of contiguous uint8 [H,W,C] CUDA tensors.  It holds raw addresses: keep
+    `dev` alive while the records are in use."""
     rec = (_lib.CropFrame * len(dev))()
     for r, im in zip(rec, dev):
         r.src, r.sh, r.sw = im.data_ptr(), int(im.size(0)), int(im.size(1))
-    return torch.frombuffer(rec, dtype=torch.uint8).to(dev[0].device)
+    return rec
+
+
+def frame_table(dev):
+    """frame_records(dev) as a device table (one small upload)"""
+    return torch.frombuffer(frame_records(dev), dtype=torch.uint8).to(dev[0].device)
 
 
 def _crops_launch(table, nframes, c, quads_ptr, row_stride, frame_stride, sel, slots, ow, oh, device, with_m9=False):

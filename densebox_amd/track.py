@@ -13,9 +13,9 @@ import itertools
 import numpy as np
 import torch
 
-from . import _lib, decode as DC
+from . import _lib, decode as DC, rows as R
 from ._lib import check, ptr, stream_ptr
-from .decode import _host, _integer, _keep_list
+from .decode import _integer, _keep_list
 
 MAX_SLOTS = 1024             # dbx_track_update_batch's bound on the list positions of a frame (they live in LDS)
 MAX_TRACKS = 256             # ... and on the track slots of a stream (one thread each)
@@ -85,6 +85,12 @@ class Tracker:
             self._records = torch.empty(self.capacity * RECORD.itemsize, dtype=torch.uint8, device=dev)
         return self._state, self._records
 
+    def _key(self, dev, first):
+        """what a captured graph that tracks the streams from `first` on depends on: the tracker, its buffers' addresses and the
+        parameters"""
+        state, records = self._buffers(dev)
+        return (first, self.serial, state.data_ptr(), records.data_ptr()) + self.params()
+
     def reset(self):
         """forget every track, id, frame count and record; the buffers (and the graphs captured on them) stay"""
         if self._state is not None:
@@ -119,11 +125,13 @@ class Tracker:
 
 
 # ------------------------------------------------------------------------------------------------------------ the launches
-def _launch(tr, dets, dc, det_rows, keep, prefix, B, slots, stream0, dry=False):
-    """dbx_track_update_batch + dbx_track_append on device tensors, for streams stream0 .. stream0 + B - 1 of tracker `tr`.  dry: the
-    launches advance a scratch copy of the state and append nothing.  Returns device tensors (ids int32 [2, B, slots] = (track_id,
-    track_hits), track_slot int32 [B, slots], retired uint8, tally int32 [B, 6])."""
-    dev = dets.device
+def _launch(tr, rows, stream0, dry=False, gallery=None):
+    """dbx_track_update_batch + dbx_track_append on the device rows `rows` (rows.Rows), for streams stream0 .. stream0 + B - 1 of tracker
+    `tr`.  gallery = (gal, crops, ok): dbx_track_gallery_update runs between the two, crops uint8 [B, slots, oh, ow, c] and ok int32
+    [B, slots] being what dbx_plate_crops_batch wrote with sel = keep.  dry: the launches advance a scratch copy of the state and
+    append nothing, and the gallery's reads it and writes nothing (commit = 0).  Returns device tensors (ids int32 [2, B, slots] =
+    (track_id, track_hits), track_slot int32 [B, slots], retired uint8, tally int32 [B, 6])."""
+    dev, B, slots = rows.dets.device, rows.B, rows.slots
     state, records = tr._buffers(dev)
     if dry:
         tr._dry.copy_(state)
@@ -135,9 +143,19 @@ def _launch(tr, dets, dc, det_rows, keep, prefix, B, slots, stream0, dry=False):
     retired = torch.empty(B * tr.max_tracks * TRACK.itemsize, dtype=torch.uint8, device=dev)
     tally = torch.empty((B, 6), dtype=torch.int32, device=dev)
     L = _lib.lib()
-    check(L.dbx_track_update_batch(ptr(dets), dc, det_rows, ptr(keep), ptr(prefix), B, slots, C.c_void_p(base), C.c_void_p(base + o_tab),
-                                   tr.streams, stream0, tr.max_tracks, tr.iou_thresh, tr.max_age, tr.alpha, tr.beta, tr.birth_score,
-                                   ptr(ids[0]), ptr(slot), ptr(ids[1]), ptr(retired), ptr(tally), stream_ptr()))
+    check(L.dbx_track_update_batch(*rows.args(), C.c_void_p(base), C.c_void_p(base + o_tab), tr.streams, stream0, tr.max_tracks,
+                                   tr.iou_thresh, tr.max_age, tr.alpha, tr.beta, tr.birth_score, ptr(ids[0]), ptr(slot), ptr(ids[1]),
+                                   ptr(retired), ptr(tally), stream_ptr()))
+    if gallery is not None:
+        from .gallery import POLICIES, SHOT, SHOT_RECORD
+        gal, crops, ok = gallery
+        live, arena, gstate = gal._buffers(dev)
+        n = tr.streams * tr.max_tracks
+        check(L.dbx_track_gallery_update(C.c_void_p(base + o_tab), C.c_void_p(base), ptr(slot), ptr(crops), ptr(ok), ptr(retired), ptr(tally),
+                                         C.c_void_p(base + o_app), ptr(live), C.c_void_p(live.data_ptr() + n * SHOT.itemsize), ptr(arena),
+                                         C.c_void_p(arena.data_ptr() + gal.capacity * SHOT_RECORD.itemsize), ptr(gstate), B, slots,
+                                         tr.streams, stream0, tr.max_tracks, gal.oh, gal.ow, gal.channels, gal.capacity,
+                                         POLICIES[gal.policy], gal.min_score, 0 if dry else 1, stream_ptr()))
     check(L.dbx_track_append(ptr(retired), ptr(tally), B, tr.max_tracks, stream0, None if dry else ptr(records), 0 if dry else tr.capacity,
                              C.c_void_p(base + o_app), stream_ptr()))
     return ids, slot, retired, tally
@@ -161,34 +179,11 @@ def update_batch(dets, keeps, *, tracker, stream0=0):
     Returns, per image, (track_id int32 [k], track_hits int32 [k]) for the k entries of its keep list in order: the id of the track the
     row continued or started (-1: none, the table was full or the row may not start one) and the number of rows that track has had."""
     fn = 'update_batch'
-    if not isinstance(dets, (list, tuple)) or not isinstance(keeps, (list, tuple)) or len(dets) != len(keeps) or not dets:
-        raise RuntimeError('%s: dets and keeps must be non-empty lists with one entry per image' % fn)
-    B = len(dets)
-    _check_streams(fn, tracker, stream0, B)
-    rows = [_host(d).astype(np.float64) for d in dets]
-    dcs = {r.shape[1] for r in rows if r.ndim == 2}
-    if any(r.ndim != 2 for r in rows) or len(dcs) != 1 or not dcs <= {5, 13}:
-        raise RuntimeError('%s: every dets entry must be [n, 5] or [n, 13], all alike; got %s' % (fn, [list(r.shape) for r in rows]))
-    dc = dcs.pop()
-    lists = [np.asarray(k, np.int64).reshape(-1) for k in keeps]
-    for i, (r, k) in enumerate(zip(rows, lists)):
-        if k.size and (k.min() < 0 or k.max() >= r.shape[0]):
-            raise RuntimeError('%s: keeps[%d] names a row outside 0..%d' % (fn, i, r.shape[0] - 1))
-    slots = max(1, max(max(r.shape[0], k.size) for r, k in zip(rows, lists)))
-    if slots > MAX_SLOTS:
-        raise RuntimeError('%s: %d rows in one image exceed %d' % (fn, slots, MAX_SLOTS))
-    nd = B * slots * dc * 8
-    host = np.zeros(nd + B * (slots + 1) * 4, np.uint8)
-    hd, hk = host[:nd].view(np.float64).reshape(B, slots, dc), host[nd:].view(np.int32).reshape(B, slots + 1)
-    for i, (r, k) in enumerate(zip(rows, lists)):
-        hd[i, :r.shape[0]] = r
-        hk[i, 0] = k.size
-        hk[i, 1:1 + k.size] = k
-    dev = tracker.device if tracker.device is not None else torch.device('cuda')
-    buf = torch.from_numpy(host).to(dev)                                              # the one upload
-    ids, _, _, _ = _launch(tracker, buf[:nd].view(torch.float64), dc, B * slots, buf[nd:].view(torch.int32), None, B, slots, int(stream0))
-    h = ids.cpu().numpy()                                                              # the one copy back
-    return [(h[0, i, :k.size].copy(), h[1, i, :k.size].copy()) for i, k in enumerate(lists)]
+    p = R.pack_host(fn, dets, keeps, max_slots=MAX_SLOTS)
+    _check_streams(fn, tracker, stream0, p.B)
+    rows = p.upload(tracker.device if tracker.device is not None else torch.device('cuda'))      # the one upload
+    h = _launch(tracker, rows, int(stream0))[0].cpu().numpy()                                      # the one copy back
+    return [(h[0, i, :k.size].copy(), h[1, i, :k.size].copy()) for i, k in enumerate(p.lists)]
 
 
 # ------------------------------------------------------------------------------------------------------------ net.track_batch
@@ -202,14 +197,8 @@ def _track_eager(tr, K, thresh, stream0, nms_thresh, dry_outside_capture):
         s, l, hm, ll = DC._forward_maps(net, images)
         B = int(images.size(0))
         dry = dry_outside_capture and not torch.cuda.is_current_stream_capturing()
-        if thresh is None:
-            dets, _, keep = DC._run_batch(s, l, K, lm_heat=hm, lm_loc=ll, nms_thresh=nms_thresh)
-            ids, slot, retired, tally = _launch(tr, dets, int(dets.size(-1)), B * K, keep, None, B, K, stream0, dry)
-            return dets, keep, ids, slot, retired, tally
-        slots = thresh[1]
-        dets, keep, counts = DC._run_thresh_batch(s, l, thresh[0], slots, hm, ll, nms_thresh, lists_behind_rows=False)
-        ids, slot, retired, tally = _launch(tr, dets, int(dets.size(-1)), B * slots, keep, counts[2 * B:], B, slots, stream0, dry)
-        return dets, keep, counts, ids, slot, retired, tally
+        rows, extra = R.decode_rows(s, l, hm, ll, B, K, thresh, nms_thresh)
+        return (rows.dets, rows.keep) + extra + _launch(tr, rows, stream0, dry)
     return eager
 
 
@@ -254,8 +243,8 @@ def track_batch(net, images, *, tracker, stream0=0, K=10, score_thresh=None, max
     fn = 'track_batch'
     _check_streams(fn, tracker, stream0, DC._frame_count(fn, images))
     tc = DC._thresh_or_topk(fn, K, score_thresh, max_dets)
-    if tc is None and (not _integer(K) or not 1 <= K <= MAX_SLOTS):
-        raise RuntimeError('%s: K=%r must be an integer in 1..%d' % (fn, K, MAX_SLOTS))
+    if tc is None:
+        R._check_K(fn, K, MAX_SLOTS)
     if tc is not None and tc[1] > MAX_SLOTS:
         raise RuntimeError('%s: max_dets=%r must be an integer in 1..%d' % (fn, max_dets, MAX_SLOTS))
     DC._one_shape(fn, images, with_dtype=True)
@@ -265,8 +254,7 @@ def track_batch(net, images, *, tracker, stream0=0, K=10, score_thresh=None, max
 
     def chunk(x, idx):
         first = int(stream0) + idx[0]
-        state, records = tracker._buffers(x.device)
-        key = (mode + (first, tracker.serial, state.data_ptr(), records.data_ptr()) + tracker.params(), float(nms_thresh))
+        key = (mode + tracker._key(x.device, first), float(nms_thresh))
         res = DC._run_chunk(net, 'track', x, key, _track_eager(tracker, int(K), tc, first, nms_thresh, dry), flags)
         return _unpack(mode[0], res, dc)
     return DC._detect_many(fn, images, max_batch, chunk, with_index=True)

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, decode as DC
+from . import _lib, decode as DC, rows as R
 from ._lib import check, ptr, stream_ptr
 from .decode import _host, _integer, _keep_list
 
@@ -94,14 +94,14 @@ def overlay_table(src, dst):
     return torch.frombuffer(rec, dtype=torch.uint8).to(src[0].device)
 
 
-def _draw_launch(table, B, c, max_h, max_w, dets, dc, det_rows, keep, prefix, slots, track_id, crops, ok, ow, oh, style):
-    """ONE dbx_draw_overlay_batch launch on the current stream over device tensors (or raw addresses given as ints); nothing is copied
-    from the host and nothing waits, so a graph capture may hold it"""
+def _draw_launch(table, c, max_h, max_w, rows, track_id, crops, ok, ow, oh, style):
+    """ONE dbx_draw_overlay_batch launch on the current stream over the device rows `rows` (rows.Rows) and device tensors (or raw
+    addresses given as ints); nothing is copied from the host and nothing waits, so a graph capture may hold it"""
     def p(t):
         return C.c_void_p(t) if isinstance(t, int) else ptr(t)
     rec = style.record()
-    check(_lib.lib().dbx_draw_overlay_batch(p(table), B, c, max_h, max_w, p(dets), dc, det_rows, p(keep), p(prefix), slots, p(track_id),
-                                            p(crops), p(ok), ow, oh, C.byref(rec), stream_ptr()))
+    check(_lib.lib().dbx_draw_overlay_batch(p(table), rows.B, c, max_h, max_w, *rows.args(batch=False), p(track_id), p(crops), p(ok), ow, oh,
+                                            C.byref(rec), stream_ptr()))
 
 
 def _up(n, a=_ALIGN):
@@ -124,20 +124,8 @@ def draw_batch(images, dets, keeps, *, track_ids=None, crops=None, ok=None, styl
     st = _style(fn, style)
     host, kinds = rectify.host_images(fn, images, None)
     B, c = len(host), int(host[0].size(2))
-    if not isinstance(dets, (list, tuple)) or not isinstance(keeps, (list, tuple)) or len(dets) != B or len(keeps) != B:
-        raise RuntimeError('%s: dets and keeps must be lists with one entry per image (%d images)' % (fn, B))
-    rows = [_host(d).astype(np.float64) for d in dets]
-    dcs = {r.shape[1] for r in rows if r.ndim == 2}
-    if any(r.ndim != 2 for r in rows) or len(dcs) != 1 or not dcs <= {5, 13}:
-        raise RuntimeError('%s: every dets entry must be [n, 5] or [n, 13], all alike; got %s' % (fn, [list(r.shape) for r in rows]))
-    dc = dcs.pop()
-    lists = [np.asarray(_host(k) if torch.is_tensor(k) else k, np.int64).reshape(-1) for k in keeps]
-    for i, (r, k) in enumerate(zip(rows, lists)):
-        if k.size and (k.min() < 0 or k.max() >= r.shape[0]):
-            raise RuntimeError('%s: keeps[%d] names a row outside 0..%d' % (fn, i, r.shape[0] - 1))
-    slots = max(1, max(max(r.shape[0], k.size) for r, k in zip(rows, lists)))
-    if slots > MAX_SLOTS:
-        raise RuntimeError('%s: %d rows in one image exceed %d' % (fn, slots, MAX_SLOTS))
+    pk = R.pack_host(fn, dets, keeps, max_slots=MAX_SLOTS, n=B)
+    lists, slots = pk.lists, pk.slots
     if track_ids is not None:
         if not isinstance(track_ids, (list, tuple)) or len(track_ids) != B:
             raise RuntimeError('%s: track_ids must be a list with one entry per image' % fn)
@@ -160,7 +148,7 @@ def draw_batch(images, dets, keeps, *, track_ids=None, crops=None, ok=None, styl
         oh, ow = next(iter(shapes))[:2]
 
     # the ONE upload: rows, keep lists, ids, flags, the frame table, then the frames that are on the host and the crops
-    nd, nk, ni = B * slots * dc * 8, B * (slots + 1) * 4, B * slots * 4
+    nd, nk, ni = pk.nd, pk.nk, B * slots * 4
     o_keep, o_ids, o_ok, o_tab = nd, nd + nk, nd + nk + ni, nd + nk + 2 * ni
     at = _up(o_tab + B * 24)
     o_src = []
@@ -180,13 +168,10 @@ def draw_batch(images, dets, keeps, *, track_ids=None, crops=None, ok=None, styl
     arena = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
     src_dev = [im.contiguous() if kind == 'cuda' else None for im, kind in zip(host, kinds)]
     h = np.zeros(total, np.uint8)
-    hd, hk = h[:nd].view(np.float64).reshape(B, slots, dc), h[o_keep:o_ids].view(np.int32).reshape(B, slots + 1)
+    pk.write(h, 0, o_keep)
     hi, ho = h[o_ids:o_ok].view(np.int32).reshape(B, slots), h[o_ok:o_tab].view(np.int32).reshape(B, slots)
     hi[:] = -1
-    for i, (r, k) in enumerate(zip(rows, lists)):
-        hd[i, :r.shape[0]] = r
-        hk[i, 0] = k.size
-        hk[i, 1:1 + k.size] = k
+    for i, k in enumerate(lists):
         if track_ids is not None:
             hi[i, :k.size] = np.clip(ids[i], -1, 2 ** 31 - 1)
         if crops is not None and k.size:
@@ -200,8 +185,8 @@ def draw_batch(images, dets, keeps, *, track_ids=None, crops=None, ok=None, styl
             h[o:o + im.numel()] = im.contiguous().numpy().reshape(-1)
     up.copy_(torch.from_numpy(h))
     base = up.data_ptr()
-    _draw_launch(base + o_tab, B, c, max(int(im.size(0)) for im in host), max(int(im.size(1)) for im in host), base, dc, B * slots,
-                 base + o_keep, None, slots, base + o_ids if track_ids is not None else None, base + o_crops if crops is not None else None,
+    _draw_launch(base + o_tab, c, max(int(im.size(0)) for im in host), max(int(im.size(1)) for im in host), pk.on(up, 0, o_keep),
+                 base + o_ids if track_ids is not None else None, base + o_crops if crops is not None else None,
                  base + o_ok if crops is not None else None, ow, oh, st)
     down = arena.cpu() if any(k != 'cuda' for k in kinds) else None        # (behind the launch on the stream: `up` and the frames are done with)
     out = []
@@ -224,7 +209,8 @@ def _annotate_eager(K, inset, tr, first, nms_thresh, style, dry_outside_capture)
         s, l, hm, ll = DC._forward_maps(net, images)
         B, H, W = int(images.size(0)), int(images.size(1)), int(images.size(2))
         dets, _, keep = DC._run_batch(s, l, K, lm_heat=hm, lm_loc=ll, nms_thresh=nms_thresh)
-        dc = int(dets.size(2))
+        rows = R.Rows(dets, keep, None, B, K)
+        dc = rows.dc
         key = (images.data_ptr(), tuple(images.shape))
         if key not in made:
             out = torch.empty_like(images)
@@ -241,10 +227,10 @@ def _annotate_eager(K, inset, tr, first, nms_thresh, style, dry_outside_capture)
         ids = None
         if tr is not None:
             dry = dry_outside_capture and not torch.cuda.is_current_stream_capturing()
-            ids, slot, retired, tally = T._launch(tr, dets, dc, B * K, keep, None, B, K, first, dry)
+            ids, slot, retired, tally = T._launch(tr, rows, first, dry)
             res.append(ids)
             rest += [slot, retired, tally]
-        _draw_launch(table, B, 3, H, W, dets, dc, B * K, keep, None, K, None if ids is None else ids[0], crops, ok, ow, oh, style)
+        _draw_launch(table, 3, H, W, rows, None if ids is None else ids[0], crops, ok, ow, oh, style)
         return tuple(res + [out] + rest)
     return eager
 
@@ -275,8 +261,7 @@ def annotate_batch(net, frames, *, tracker=None, stream0=0, inset=None, K=10, nm
                            % (fn, sorted({str(tuple(im.shape)) for im in host})))
     if tracker is not None:
         T._check_streams(fn, tracker, stream0, len(host))
-    if not _integer(K) or not 1 <= K <= MAX_SLOTS:
-        raise RuntimeError('%s: K=%r must be an integer in 1..%d' % (fn, K, MAX_SLOTS))
+    R._check_K(fn, K, MAX_SLOTS)
     if not _integer(max_batch) or max_batch < 1:
         raise RuntimeError('%s: max_batch=%r must be a positive integer' % (fn, max_batch))
     if inset is not None:
@@ -291,8 +276,7 @@ def annotate_batch(net, frames, *, tracker=None, stream0=0, inset=None, K=10, nm
         first = int(stream0) + idx[0]
         key = ('topk', K, inset, st.key(), to_host)
         if tracker is not None:
-            state, records = tracker._buffers(x.device)
-            key += (first, tracker.serial, state.data_ptr(), records.data_ptr()) + tracker.params()
+            key += tracker._key(x.device, first)
         eager = _annotate_eager(K, inset, tracker, first, nms_thresh, st, dry)
         n_res = 4 if tracker is not None else 3
         n_rest = 1 + (3 if inset else 0) + (3 if tracker is not None else 0)

@@ -12,7 +12,8 @@ import pytest
 import torch
 
 import densebox_amd as D
-from densebox_amd import _lib, evaluate as E, synth
+from densebox_amd import _lib, decode as DC, evaluate as E, synth
+from densebox_amd.rows import Rows
 from densebox_amd._lib import check, ptr, stream_ptr
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -201,7 +202,7 @@ def _thresh_decode(counts, cap=64):
     the host (rows, keep list)"""
     images = [thresh_ref.craft_maps(40 + i, 16, 16, n, 4) for i, n in enumerate(counts)]
     maps = {k: torch.from_numpy(np.ascontiguousarray(np.concatenate([m[k] for m in images]))).cuda() for k in images[0]}
-    dets, keep, cnt = E._run_thresh_lists(maps['score'], maps['loc'], 0.5, cap, maps['lm_heat'], maps['lm_loc'], 0.4)
+    dets, keep, cnt = DC._run_thresh_batch(maps['score'], maps['loc'], 0.5, cap, maps['lm_heat'], maps['lm_loc'], 0.4, lists_behind_rows=False)
     torch.cuda.synchronize()
     B = len(counts)
     c, d, k = cnt.cpu().numpy(), dets.cpu().numpy(), keep.cpu().numpy()
@@ -278,7 +279,7 @@ def test_append_orders_records_counts_totals_and_drops_beyond_capacity():
     dets, keep = _slot_inputs(rows, lists, slots, dc)
     o_cnt, o_ign, _ = E._gt_layout(B, 3, 12)
     gtbuf = torch.from_numpy(E._pack_gt(frames, 3, 12)).cuda()
-    status, index, iou, err, tally = E._launch_match(dets, dc, B * slots, keep, None, B, slots, gtbuf, 12, 3, 0.5)
+    status, index, iou, err, tally = E._launch_match(Rows(dets, keep, None, B, slots), gtbuf, 12, 3, 0.5)
     ref = [R.match_frame(rows[b], lists[b], *frames[b], 0.5) for b in range(B)]
     want = R.records([(rows[b], lists[b], ref[b][0], ref[b][3]) for b in range(B)])
     assert len(want) == 12

@@ -12,7 +12,8 @@ import pytest
 import torch
 
 import densebox_amd as D
-from densebox_amd import _lib, evaluate as E, synth, track as T
+from densebox_amd import _lib, decode as DC, synth, track as T
+from densebox_amd.rows import Rows
 from densebox_amd._lib import check, ptr, stream_ptr
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -191,7 +192,7 @@ def _thresh_decode(counts, cap=64):
     the host (rows, keep list)"""
     images = [thresh_ref.craft_maps(40 + i, 16, 16, n, 4) for i, n in enumerate(counts)]
     maps = {k: torch.from_numpy(np.ascontiguousarray(np.concatenate([m[k] for m in images]))).cuda() for k in images[0]}
-    dets, keep, cnt = E._run_thresh_lists(maps['score'], maps['loc'], 0.5, cap, maps['lm_heat'], maps['lm_loc'], 0.4)
+    dets, keep, cnt = DC._run_thresh_batch(maps['score'], maps['loc'], 0.5, cap, maps['lm_heat'], maps['lm_loc'], 0.4, lists_behind_rows=False)
     torch.cuda.synchronize()
     B = len(counts)
     c, d, k = cnt.cpu().numpy(), dets.cpu().numpy(), keep.cpu().numpy()
@@ -258,7 +259,7 @@ def test_append_orders_records_counts_totals_and_drops_beyond_capacity():
         R.append(astate, records, 64, want, 2)
         dets, keep = _slot_inputs(frames, slots, dc)
         for tr in (big, small):
-            T._launch(tr, dets, dc, B * slots, keep, None, B, slots, 2)
+            T._launch(tr, Rows(dets, keep, None, B, slots), 2)
     assert astate.tolist() == [20, 0, 20, 0]
     got = big.finished()
     assert got.shape == (20,) and np.array_equal(_bits(got), _bits(R.as_records(records)))

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 import densebox_amd as D
-from densebox_amd import _lib, evaluate as E, synth, track as T, viz
+from densebox_amd import _lib, decode as DC, synth, track as T, viz
 from densebox_amd._lib import check, ptr, stream_ptr
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -220,7 +220,7 @@ def _thresh_decode(counts, cap=64):
     the host (rows, keep list)"""
     images = [thresh_ref.craft_maps(40 + i, 16, 16, n, 4) for i, n in enumerate(counts)]
     maps = {k: torch.from_numpy(np.ascontiguousarray(np.concatenate([m[k] for m in images]))).cuda() for k in images[0]}
-    dets, keep, cnt = E._run_thresh_lists(maps['score'], maps['loc'], 0.5, cap, maps['lm_heat'], maps['lm_loc'], 0.4)
+    dets, keep, cnt = DC._run_thresh_batch(maps['score'], maps['loc'], 0.5, cap, maps['lm_heat'], maps['lm_loc'], 0.4, lists_behind_rows=False)
     torch.cuda.synchronize()
     B = len(counts)
     c, d, k = cnt.cpu().numpy(), dets.cpu().numpy(), keep.cpu().numpy()

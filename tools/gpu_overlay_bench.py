@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 import densebox_amd as D
-from densebox_amd import synth, track, viz
+from densebox_amd import rows, synth, track, viz
 
 H, W, B, K = 512, 512, 32, 10
 
@@ -134,8 +134,10 @@ def main():
         out = torch.empty_like(x)
         table = viz.overlay_table(list(x.unbind(0)), list(out.unbind(0)))
 
+        drows = rows.Rows(d, keep, None, B, K)
+
         def launch():
-            viz._draw_launch(table, B, 3, H, W, d, 13, B * K, keep, None, K, ids, None, None, 0, 0, style)
+            viz._draw_launch(table, 3, H, W, drows, ids, None, None, 0, 0, style)
 
         def copy():
             out.copy_(x)
