@@ -113,6 +113,24 @@ class PatchPlanIO(C.Structure):
         'status', 'slot', 'cand_out', 'draws_out')]
 
 
+class PatchAug(C.Structure):
+    _fields_ = [('flags', C.c_int32), ('blur', C.c_int32), ('box_len', C.c_int32), ('sat', C.c_int32), ('contrast', C.c_int32),
+                ('brightness', C.c_int32), ('curve', C.c_int32), ('noise_amp', C.c_int32), ('key_lo', C.c_int32), ('key_hi', C.c_int32),
+                ('gain', C.c_int32 * 3), ('reserved', C.c_int32 * 3)]
+
+
+class PatchAugCfg(C.Structure):
+    _fields_ = [('p_flip', C.c_double), ('p_blur', C.c_double), ('p_curve', C.c_double), ('p_noise', C.c_double), ('kind_w', C.c_int32 * 3),
+                ('box_lo', C.c_int32), ('box_hi', C.c_int32), ('sat_lo', C.c_int32), ('sat_hi', C.c_int32), ('contrast_lo', C.c_int32),
+                ('contrast_hi', C.c_int32), ('brightness_lo', C.c_int32), ('brightness_hi', C.c_int32), ('gain_lo', C.c_int32),
+                ('gain_hi', C.c_int32), ('noise_lo', C.c_int32), ('noise_hi', C.c_int32), ('curve_lo', C.c_int32), ('curve_hi', C.c_int32),
+                ('G', C.c_int32), ('reserved', C.c_int32 * 2)]
+
+
+class PatchAugIO(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ('labels_in', 'count', 'params_in', 'state', 'params', 'labels', 'bbox', 'vertices', 'label')]
+
+
 class MergeXform(C.Structure):
     _fields_ = [('scale', C.c_double), ('off_x', C.c_double), ('off_y', C.c_double)]
 
@@ -184,6 +202,10 @@ SIGNATURES = {
     'dbx_patch_plan_host': (C.c_int, [_I32, _I32, _I32, _VP, _I32, _D, _D, _D, _I32, C.POINTER(PatchGeom)]),
     'dbx_patch_draw': (C.c_int, [_I64, _I64, _I32, _I32, _VP]),
     'dbx_patch_check_tables': (C.c_int, [_VP, _I32, _VP, _I32, _VP, _I32]),
+    'dbx_patch_aug_plan': (C.c_int, [C.POINTER(PatchAugIO), C.POINTER(PatchAugCfg), _I32, _VP]),
+    'dbx_patch_augment': (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP]),
+    'dbx_patch_aug_params_host': (C.c_int, [C.POINTER(PatchAugCfg), _I64, _I64, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP]),
+    'dbx_patch_augment_host': (C.c_int, [_VP, _VP, _VP, _I32, _I32, _VP]),
     'dbx_conv_wgrad_scratch_bytes': (_I64, [_I32, _PV, _PV, _I32, _I32]),
     'dbx_conv_wgrad': (C.c_int, [_I32, _PV, _PV, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _I32, _VP]),
     'dbx_conv_wgrad_slice': (C.c_int, [_I32, _PV, _PV, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP]),

@@ -10,6 +10,7 @@
 // k = h >> 11 is the 53-bit draw: a uniform is -1.0 + 2.0 * (k * 2^-53), an integer in a range of r values is k mod r.
 #pragma clang fp contract(off)
 #include "common.hpp"
+#include "patch_hash.hpp"
 #include "resize_tile.hpp"
 
 #include <math.h>
@@ -23,16 +24,6 @@ static_assert(sizeof(dbx_patch_geom) == 72 && sizeof(dbx_patch_plan_io) == 136, 
 #define PATCH_THREADS 256
 #define PATCH_TILES_X ((DBX_PATCH_SIDE + RSZ_TW - 1) / RSZ_TW)
 #define PATCH_TILES (PATCH_TILES_X * ((DBX_PATCH_SIDE + RSZ_TH - 1) / RSZ_TH))
-
-__host__ __device__ inline uint64_t patch_mix(uint64_t x) {
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
-    return x;
-}
-__host__ __device__ inline uint64_t patch_hash(int64_t seed, int64_t counter, int i, int j) {
-    const uint64_t a = patch_mix((uint64_t)seed + 0x9E3779B97F4A7C15ull * ((uint64_t)counter + 1ull));
-    return patch_mix(a + 0xD1B54A32D192ED03ull * ((uint64_t)i + 1ull) + 0x8CB92BA72F3D8DD7ull * ((uint64_t)j + 1ull));
-}
-__host__ __device__ inline double patch_unit(uint64_t h) { return (double)(h >> 11) * (1.0 / 9007199254740992.0); }     // k * 2^-53
 
 // int(x + 0.5) of the reference: truncation toward zero; saturated where a Python int would go on growing
 __host__ __device__ inline int patch_round(double x) {

@@ -194,12 +194,143 @@ def sample_patches(frames, plates, n, candidates=None, draws=None, neg_frac=0.1,
     return patches, plan
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# Photometric augmentation and horizontal flip of the cut patches on the device (dbx_patch_aug_plan + dbx_patch_augment;
+# include/densebox_hip.h, "training patch augmentation").  The reference has no augmentation: the semantics are this project's own,
+# restated in tests/aug_ref.py.
+AUG_FIELDS = ('flags', 'blur', 'box_len', 'sat', 'contrast', 'brightness', 'curve', 'noise_amp', 'key_lo', 'key_hi', 'gain0', 'gain1', 'gain2',
+              'reserved0', 'reserved1', 'reserved2')
+
+
+def _q8(v):
+    return int(round(float(v) * 256.0))
+
+
+class Augment(object):
+    """A plain config of the augmentation: probabilities and ranges, from which cfg() makes the dbx_patch_aug_cfg struct and curves()
+    the uint8 [G, 256] bank of rounded gamma curves.  flip / blur / curve / noise_p: probabilities; saturation, contrast, gain:
+    (lo, hi) factors, held in Q8; brightness: (lo, hi) grey levels; noise: (lo, hi) of the record's Q8 amplitude, which is also the peak
+    deviation in grey levels; blur_kinds: integer weights of (binomial 3 x 3, binomial 5 x 5, horizontal box); box: (lo, hi) odd box
+    lengths.  The defaults are a convention, not tuned: there are no trained weights in this tree to tune them against."""
+
+    def __init__(self, flip=0.5, blur=0.3, saturation=(0.6, 1.4), contrast=(0.7, 1.3), brightness=(-32, 32), gain=(0.9, 1.1),
+                 gammas=(0.6, 0.8, 1.25, 1.6), curve=0.3, noise=(0, 12), noise_p=0.5, seed=0, blur_kinds=(1, 1, 1), box=(3, 9)):
+        self.flip, self.blur, self.curve, self.noise_p, self.seed = float(flip), float(blur), float(curve), float(noise_p), int(seed)
+        self.saturation, self.contrast, self.gain = tuple(saturation), tuple(contrast), tuple(gain)
+        self.brightness, self.noise, self.gammas = tuple(brightness), tuple(noise), tuple(float(g) for g in gammas)
+        self.blur_kinds, self.box = tuple(int(w) for w in blur_kinds), tuple(int(b) for b in box)
+        self._bank = None
+
+    @classmethod
+    def identity(cls, seed=0):
+        """The no-op: every record it draws is the identity record, and the kernel copies."""
+        return cls(flip=0.0, blur=0.0, saturation=(1.0, 1.0), contrast=(1.0, 1.0), brightness=(0, 0), gain=(1.0, 1.0), gammas=(), curve=0.0,
+                   noise=(0, 0), noise_p=0.0, seed=seed)
+
+    def cfg(self):
+        f = _lib.PatchAugCfg()
+        f.p_flip, f.p_blur, f.p_curve, f.p_noise = self.flip, self.blur, self.curve, self.noise_p
+        f.kind_w[:] = self.blur_kinds
+        f.box_lo, f.box_hi = self.box
+        f.sat_lo, f.sat_hi = _q8(self.saturation[0]), _q8(self.saturation[1])
+        f.contrast_lo, f.contrast_hi = _q8(self.contrast[0]), _q8(self.contrast[1])
+        f.brightness_lo, f.brightness_hi = int(self.brightness[0]), int(self.brightness[1])
+        f.gain_lo, f.gain_hi = _q8(self.gain[0]), _q8(self.gain[1])
+        f.noise_lo, f.noise_hi = int(self.noise[0]), int(self.noise[1])
+        f.G = len(self.gammas)
+        f.curve_lo, f.curve_hi = 0, max(f.G - 1, 0)
+        return f
+
+    def curves(self):
+        """uint8 [G, 256]: round(255 * (v / 255) ** gamma), made once on the host."""
+        if self._bank is None:
+            v = np.arange(256, dtype=np.float64) / 255.0
+            self._bank = (np.stack([np.rint(255.0 * v ** g) for g in self.gammas]).astype(np.uint8) if self.gammas
+                          else np.zeros((0, 256), np.uint8))
+        return self._bank
+
+
+class AugPlan(object):
+    """The device tensors one dbx_patch_aug_plan launch writes: params int32 [n, 16] (dbx_patch_aug records, AUG_FIELDS), labels_i32 int32
+    [n, 12], bbox float32 [n, 4], vertices [n, 8], labels [n, 1].  Rows at or past the count are not written (the tensors start zeroed)."""
+
+    def __init__(self, n, device):
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+        self.n = int(n)
+        self.params, self.labels_i32 = z((n, 16), torch.int32), z((n, 12), torch.int32)
+        self.bbox, self.vertices, self.labels = z((n, 4), torch.float32), z((n, 8), torch.float32), z((n, 1), torch.float32)
+
+
+def plan_augment(labels_i32, count, cfg, params=None, state=None, out=None):
+    """The dbx_patch_aug_plan launch alone, on the current stream.  labels_i32 int32 [n, 12] and count int32 [1]: device tensors (a
+    PatchPlan's); cfg: Augment.cfg(); params int32 [n, 16] (injected mode) or state int64 [2] = (seed, counter) (device mode), device
+    tensors.  Returns the AugPlan (`out`, or a new one)."""
+    n = int(labels_i32.size(0))
+    out = out if out is not None else AugPlan(n, labels_i32.device)
+    io = _lib.PatchAugIO()
+    io.labels_in, io.count = labels_i32.data_ptr(), count.data_ptr()
+    io.params_in = params.data_ptr() if params is not None else None
+    io.state = state.data_ptr() if state is not None else None
+    io.params, io.labels, io.bbox, io.vertices, io.label = out.params.data_ptr(), out.labels_i32.data_ptr(), out.bbox.data_ptr(), \
+        out.vertices.data_ptr(), out.labels.data_ptr()
+    _lib.check(_lib.lib().dbx_patch_aug_plan(C.byref(io), C.byref(cfg), n, _lib.stream_ptr()))
+    return out
+
+
+def apply_augment(patches, params, count, curves, out=None):
+    """The dbx_patch_augment launch alone: patches uint8 [n, 240, 240, c] (any byte alignment) through the records params int32 [n, 16]
+    into `out` (a new zeroed tensor when None; it may not overlap patches).  curves: device uint8 [G, 256].  Slots at or past the count keep
+    what they held."""
+    if patches.dtype != torch.uint8 or patches.dim() != 4 or tuple(patches.shape[1:3]) != (PATCH_SIDE, PATCH_SIDE) or not patches.is_contiguous():
+        raise RuntimeError('apply_augment: patches must be a contiguous uint8 [n, 240, 240, c] tensor, got %s %s' % (patches.dtype, list(patches.shape)))
+    if out is None:
+        out = torch.zeros_like(patches)
+    if out.dtype != torch.uint8 or out.shape != patches.shape or not out.is_contiguous():
+        raise RuntimeError('apply_augment: out must be a contiguous uint8 %s tensor, got %s %s' % (list(patches.shape), out.dtype, list(out.shape)))
+    G = int(curves.size(0))
+    _lib.check(_lib.lib().dbx_patch_augment(C.c_void_p(patches.data_ptr()), C.c_void_p(params.data_ptr()), C.c_void_p(count.data_ptr()),
+                                            C.c_void_p(curves.data_ptr()) if G else None, G, int(patches.size(0)), int(patches.size(3)),
+                                            C.c_void_p(out.data_ptr()), _lib.stream_ptr()))
+    return out
+
+
+def augment_patches(patches, plan_or_labels, augment=None, params=None, counter=0):
+    """One upload + the two launches, for patches a user already has.  patches: uint8 [n, 240, 240, c], host or device; plan_or_labels: a
+    PatchPlan (its label rows and count) or the int [n, 12] label rows (then all n slots count); augment: an Augment (None: the
+    default one); params: int [n, 16] records (injected mode), else they are drawn from (augment.seed, counter).  Returns (out,
+    labels_i32, bbox, vertices, labels, params): the augmented patches, the four label tensors and the records used."""
+    augment = augment if augment is not None else Augment()
+    dev = patches if torch.is_tensor(patches) else torch.from_numpy(np.ascontiguousarray(patches))
+    dev = dev.cuda()
+    n = int(dev.size(0))
+    parts = [augment.curves().reshape(-1) if len(augment.gammas) else np.zeros(256, np.uint8), np.array([augment.seed, counter], dtype=np.int64)]
+    if params is not None:
+        rec = params.cpu().numpy() if torch.is_tensor(params) else np.asarray(params)
+        parts.append(np.ascontiguousarray(rec.astype(np.int32).reshape(n, 16)))
+    if isinstance(plan_or_labels, PatchPlan):
+        labels_in, count = plan_or_labels.labels_i32, plan_or_labels.count
+    else:
+        rows = plan_or_labels.cpu().numpy() if torch.is_tensor(plan_or_labels) else np.asarray(plan_or_labels)
+        parts += [np.ascontiguousarray(rows.astype(np.int32).reshape(n, 12)), np.array([n], dtype=np.int32)]
+        labels_in = count = None
+    up = _upload(*parts)
+    curves = up[0].view(-1, 256)[:len(augment.gammas)]
+    if labels_in is None:
+        labels_in, count = up[-2], up[-1]
+    plan = plan_augment(labels_in, count, augment.cfg(), params=up[2] if params is not None else None, state=up[1])
+    out = apply_augment(dev, plan.params, count, curves)
+    return out, plan.labels_i32, plan.bbox, plan.vertices, plan.labels, plan.params
+
+
 class PatchSampler(object):
     """Fresh training patches every step with frames, tables, state and outputs resident on the device.  frames / plates: as for
     sample_patches; n: patches per batch; every batch decides ceil(oversample * n) candidates (at most 4096), of which a fraction
-    neg_frac are pure negatives.  next_batch() is the two launches plus a 4-byte read of the count."""
+    neg_frac are pure negatives.  next_batch() is the two launches plus a 4-byte read of the count.  augment: an Augment; then
+    launch() adds dbx_patch_aug_plan + dbx_patch_augment after the cut, into a second buffer of the sampler's, and next_batch() returns
+    the augmented patches and labels; `raw` and `plan` still hold the un-augmented ones, `aug_params` the records used (int32 [n, 16]).
+    The augmenter's state (augment.seed, counter) is its own: the plan's draws do not depend on it."""
 
-    def __init__(self, frames, plates, n, oversample=1.5, neg_frac=0.1, seed=0, offset_radius=15, th=0, allow_short=False):
+    def __init__(self, frames, plates, n, oversample=1.5, neg_frac=0.1, seed=0, offset_radius=15, th=0, allow_short=False, augment=None):
         if int(n) < 1 or not oversample >= 1.0:
             raise RuntimeError('PatchSampler: n=%r must be positive and oversample=%r at least 1' % (n, oversample))
         host, _ = host_images('PatchSampler', frames, None)
@@ -213,13 +344,34 @@ class PatchSampler(object):
         self.plan = PatchPlan(self.M, self.n, self.table.device)
         self.patches = torch.zeros((self.n, PATCH_SIDE, PATCH_SIDE, self.c), dtype=torch.uint8, device=self.table.device)
         self.totals = torch.zeros(8, dtype=torch.int64, device=self.table.device)
+        self.augment = augment
+        if augment is not None:
+            bank = augment.curves()
+            self.curves, self.aug_state = _upload(bank.reshape(-1) if len(bank) else np.zeros(256, np.uint8),
+                                                  np.array([augment.seed, 0], dtype=np.int64))
+            self.curves = self.curves.view(-1, 256)[:len(bank)]
+            self.aug_cfg = augment.cfg()
+            self.aug = AugPlan(self.n, self.table.device)
+            self.aug_patches = torch.zeros_like(self.patches)
+
+    @property
+    def raw(self):
+        """The un-augmented patches of the last batch (the sampler's own buffer)."""
+        return self.patches
+
+    @property
+    def aug_params(self):
+        return self.aug.params if self.augment is not None else None
 
     def launch(self):
-        """The two launches (and the tally's accumulation) on the current stream, without any read: what a graph capture holds."""
+        """The launches (and the tally's accumulation) on the current stream, without any read: what a graph capture holds."""
         plan_patches(self.table, len(self.frames), self.c, self.plates, self.plate0, self.M, self.n, state=self.state,
                      neg_frac=self.neg_frac, offset_radius=self.offset_radius, th=self.th, out=self.plan)
         cut_patches(self.plan, self.c, self.patches)
         self.totals += self.plan.tally
+        if self.augment is not None:
+            plan_augment(self.plan.labels_i32, self.plan.count, self.aug_cfg, state=self.aug_state, out=self.aug)
+            apply_augment(self.patches, self.aug.params, self.plan.count, self.curves, self.aug_patches)
 
     def next_batch(self, allow_short=None):
         """(patches uint8 [n, 240, 240, C], bbox [n, 4], vertices [n, 8], labels [n, 1], count): net.forward's and net.loss's inputs.
@@ -230,6 +382,8 @@ class PatchSampler(object):
         if count < self.n and not (self.allow_short if allow_short is None else allow_short):
             raise RuntimeError('PatchSampler: %d of %d candidates were accepted, fewer than n=%d; raise oversample (status tally: %s)'
                                % (count, self.M, self.n, self.plan.tally.tolist()))
+        if self.augment is not None:
+            return self.aug_patches, self.aug.bbox, self.aug.vertices, self.aug.labels, count
         return self.patches, self.plan.bbox, self.plan.vertices, self.plan.labels, count
 
     def status_tally(self):

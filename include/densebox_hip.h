@@ -1024,6 +1024,101 @@ int dbx_patch_draw(int64_t seed, int64_t counter, int32_t i0, int32_t count, uin
  * 0 .. n_plates - 1, a negative's index outside 0 .. n_frames - 1. */
 int dbx_patch_check_tables(const int32_t* plates, int32_t n_plates, const int32_t* plate0, int32_t n_frames, const int32_t* cand, int32_t M);
 
+/* ---- training patch augmentation (this project's own semantics: the reference has none; tests/aug_ref.py restates them in NumPy) ----
+ * Two launches after dbx_patch_cut and no host read: dbx_patch_aug_plan (ONE workgroup) decides a parameter record per slot and writes
+ * the labels that go with it; dbx_patch_augment (n * 15 workgroups, fixed by n alone) makes the augmented patches, out of place.  All
+ * pixel arithmetic is integer, every shift is arithmetic (a floor), clamp is to 0..255: the kernel equals the restatement bit for bit.
+ *
+ * dbx_patch_aug (64 bytes, 16 int32): flags 0 (bit 0: flip applied, bit 1: flip refused), blur 4 (0 none, 1 binomial 3 x 3, 2 binomial
+ * 5 x 5, 3 horizontal box), box_len 8 (odd, 3..9; read by blur 3 only), sat 12 (Q8, 256 = identity), contrast 16 (Q8), brightness 20
+ * (-255..255), curve 24 (a row of the bank, -1 = none), noise_amp 28 (Q8, 0 = none), key_lo 32, key_hi 36 (the low and the high half of
+ * the 64-bit noise key), gain 40 (3 x Q8, one per colour channel), reserved 52 (3 x 0).
+ * What a kernel reads of a record ("sanitised", the same function on host and device): flags & 3; a blur outside 0..3, or blur 3 with a
+ * box_len that is even or outside 3..9, is blur 0; sat, contrast, gain and noise_amp are clamped to 0..65535, brightness to -255..255; a
+ * curve outside 0 .. G - 1 is -1 (no kernel follows it); reserved is 0.  The records written out are the sanitised ones.
+ *
+ * A pixel (x, y) of a patch with c channels; the colour channels are the first min(c, 3), a fourth channel is flipped and blurred and
+ * otherwise copied.  In this order:
+ *   1. flip: with bit 0 the image is mirrored, I'(x, y) = I(239 - x, y).
+ *   2. blur of the (mirrored) image, edges replicated (coordinates clamped to 0..239):
+ *        blur 1: weights outer([1, 2, 1]), v = (sum + 8) >> 4;  blur 2: outer([1, 4, 6, 4, 1]), v = (sum + 128) >> 8 -- one rounding;
+ *        blur 3: the box_len pixels of the row centred on x, v = (2 * sum + L) / (2 * L) in integer division.
+ *   3. saturation, when c >= 3: Y = (v0 + 2 * v1 + v2 + 2) >> 2 (the gallery's luma weights, free of the channel order);
+ *        v_k = clamp(Y + (((v_k - Y) * sat + 128) >> 8)).
+ *   4. tone, per colour channel k: g = clamp((v * gain_k + 128) >> 8); t = clamp((((g - 128) * contrast + 128) >> 8) + 128 + brightness);
+ *        with curve >= 0: t = curves[curve][t].  (The kernel composes a 256-entry table per colour channel.)
+ *   5. noise, when noise_amp > 0: h = mix(key + 0x9E3779B97F4A7C15 * (y * 240 + x + 1)) with the sampler's mix and unsigned 64-bit
+ *        wrapping, (x, y) the OUTPUT pixel; t_k = byte(h, 2k) + byte(h, 2k + 1) - 255 with byte(h, j) = (h >> 8j) & 255;
+ *        d = t_k * noise_amp; the term is (d + 128) >> 8 for d >= 0 and -((-d + 128) >> 8) for d < 0 (half away from zero on both
+ *        sides: a plain (d + 128) >> 8 rounds every half upward and has a mean of up to +1/4); v_k = clamp(v_k + term).
+ * curves: device uint8 [G][256], made on the host (no pow on the device); may be NULL when G == 0.
+ *
+ * Labels.  labels_in int32 [n][12] = (bx0, by0, bx1, by1, lu, ru, rd, ld) as dbx_patch_plan wrote them; a row of twelve zeros is a
+ * negative.  Without a flip the row is copied.  A flip of a positive: bx0' = 239 - bx1, bx1' = 239 - bx0, lu' = (239 - ru.x, ru.y),
+ * ru' = (239 - lu.x, lu.y), rd' = (239 - ld.x, ld.y), ld' = (239 - rd.x, rd.y), every y as it was.  The plan's labels may be 240 on the
+ * right edge: a positive with any of its six x values outside 0..239 is NOT flipped, pixels included; bit 0 is cleared and bit 1 set.  A
+ * negative flips its pixels and keeps its zero row.  bbox = labels[0..3] / 4, vertices = labels[4..11] / 4 and label = 1 (0 for a
+ * negative) as float32, exactly as dbx_patch_plan writes them.  Rows at or past min(count, n) are not written.
+ *
+ * Parameters.
+ *   injected mode (io->params_in non-NULL): slot s reads params_in[s]; flags bit 0 asks for the flip, bit 1 is ignored.
+ *   device mode (params_in NULL): from h(seed, counter, s, j) of the sampler's hash with a FIXED draw number j per field, k = h >> 11; "on
+ *   with probability p" is k * 2^-53 < p; a range is lo + k mod (hi - lo + 1):
+ *     j = 0 flip on (p_flip);  1 blur on (p_blur);  2 blur kind: w = k mod (kind_w[0] + kind_w[1] + kind_w[2]), kind 1 when w < kind_w[0],
+ *     2 when w < kind_w[0] + kind_w[1], else 3;  3 box_len = box_lo + 2 * (k mod ((box_hi - box_lo) / 2 + 1));  4 sat;  5 contrast;
+ *     6 brightness;  7 curve on (p_curve);  8 curve = curve_lo + k mod (curve_hi - curve_lo + 1);  9 noise on (p_noise);  10 noise_amp;
+ *     11 the key (the whole hash);  12, 13, 14 gain[0..2].
+ *   An op that is off writes its neutral value (blur 0, curve -1, noise_amp 0); box_len and the key are always the drawn ones.
+ *   state = device int64 [2] = (seed, counter), the augmenter's own; the launch's last act is counter += 1, so a replay draws anew.
+ *   Both modes write the records they used to io->params.
+ * dbx_patch_aug_cfg (112 bytes): p_flip 0, p_blur 8, p_curve 16, p_noise 24 (double); kind_w 32 (3 x int32); box_lo 44, box_hi 48; sat_lo
+ * 52, sat_hi 56; contrast_lo 60, contrast_hi 64; brightness_lo 68, brightness_hi 72; gain_lo 76, gain_hi 80; noise_lo 84, noise_hi 88;
+ * curve_lo 92, curve_hi 96; G 100 (rows of the bank); reserved 104 (2 x 0). */
+typedef struct dbx_patch_aug {
+    int32_t flags, blur, box_len, sat, contrast, brightness, curve, noise_amp;
+    int32_t key_lo, key_hi;
+    int32_t gain[3];
+    int32_t reserved[3];
+} dbx_patch_aug;
+typedef struct dbx_patch_aug_cfg {
+    double p_flip, p_blur, p_curve, p_noise;
+    int32_t kind_w[3];
+    int32_t box_lo, box_hi, sat_lo, sat_hi, contrast_lo, contrast_hi, brightness_lo, brightness_hi, gain_lo, gain_hi, noise_lo, noise_hi;
+    int32_t curve_lo, curve_hi, G;
+    int32_t reserved[2];
+} dbx_patch_aug_cfg;
+/* device pointers of dbx_patch_aug_plan (72 bytes: 9 pointers in this order) */
+typedef struct dbx_patch_aug_io {
+    const int32_t* labels_in;          /* [n][12] */
+    const int32_t* count;              /* [1] */
+    const dbx_patch_aug* params_in;    /* [n], or NULL: device mode */
+    int64_t* state;                    /* [2] (seed, counter); needed in device mode only */
+    dbx_patch_aug* params;             /* [n] */
+    int32_t* labels;                   /* [n][12] */
+    float* bbox;                       /* [n][4] */
+    float* vertices;                   /* [n][8] */
+    float* label;                      /* [n][1] */
+} dbx_patch_aug_io;
+/* cfg is a HOST struct, needed in both modes (injected mode reads G alone).  Refused with DBX_ERR_ARG before anything is queued: a null
+ * io, cfg or pointer (params_in may be NULL: device mode, which needs state), n outside 1..4096, and a cfg with: a p outside [0, 1], G
+ * outside 0..65536, a kind weight outside 0..2^20 or -- with p_blur > 0 -- none positive, a box length that is even or outside 3..9, a range
+ * with lo > hi, sat / contrast / gain / noise outside 0..65535, brightness outside -255..255, with p_curve > 0 a curve index range that
+ * leaves the bank (0 <= curve_lo <= curve_hi < G). */
+int dbx_patch_aug_plan(const dbx_patch_aug_io* io, const dbx_patch_aug_cfg* cfg, int32_t n, void* stream);
+/* patches, out: device uint8 [n][240][240][c] at any byte address; params / count as dbx_patch_aug_plan left them (or any records: they
+ * are sanitised).  Slot s < min(count, n) is written, every other byte of out is left alone.  Out of place only: a blurred band reads its
+ * neighbours' rows.  Refused: a null pointer (curves may be NULL when G == 0), c outside 1..4, n outside 1..4096, G outside 0..65536,
+ * patches and out overlapping. */
+int dbx_patch_augment(const uint8_t* patches, const dbx_patch_aug* params, const int32_t* count, const uint8_t* curves, int32_t G,
+                      int32_t n, int32_t c, uint8_t* out, void* stream);
+/* dbx_patch_aug_plan on the host (the same __host__ __device__ functions) for slots 0 .. count - 1, count in 0..4096: params_in NULL
+ * derives from (seed, counter).  Refusals as for dbx_patch_aug_plan. */
+int dbx_patch_aug_params_host(const dbx_patch_aug_cfg* cfg, int64_t seed, int64_t counter, const dbx_patch_aug* params_in,
+                              const int32_t* labels_in, int32_t count, dbx_patch_aug* params, int32_t* labels, float* bbox,
+                              float* vertices, float* label);
+/* dbx_patch_augment of ONE patch [240][240][c] on the host.  Refusals as for dbx_patch_augment. */
+int dbx_patch_augment_host(const uint8_t* patch, const dbx_patch_aug* rec, const uint8_t* curves, int32_t G, int32_t c, uint8_t* out);
+
 /* ---- data-parallel gradient exchange (new capability; the reference is single-GPU) ----
  * One process per GPU.  Rank 0 makes a 128-byte id (dbx_dp_unique_id) and hands it to the other ranks by any host channel;
  * every rank calls dbx_dp_init with its HIP device current; after each backward, dbx_dp_allreduce_sum_f32 sums the flat fp32
