@@ -53,6 +53,11 @@ __device__ __forceinline__ int lm_coord(float v, int clamp) {          // int(co
     if (clamp) x = x < HWD ? x : HWD - 1;
     return x;
 }
+// pixel index of a landmark, or -1 when its rounded (and clamped) x or y is outside the grid: such a landmark is never used as an index --
+// the channel then has no positive pixel and no gray zone ("The fused loss at the edges of the grid": the reference wraps -60..-1 and raises beyond)
+__device__ __forceinline__ int lm_pixel(int x, int y) {
+    return (x >= 0 && x < HWD && y >= 0 && y < HWD) ? y * HWD + x : -1;
+}
 
 // block-wide arg-max of (value, lowest index on ties) over smem[0..NPIX); result broadcast via red_i[0]
 __device__ __forceinline__ int block_argmax(const float* vals, float* red_v, int* red_i) {
@@ -218,7 +223,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_kernel(const LossArgs a) {
         for (int j = 0; j < 4; ++j) { lmx[j] = lm_coord(vt[2 * j], clamp); lmy[j] = lm_coord(vt[2 * j + 1], clamp); }
         for (int j = 0; j < 4; ++j) {
             const float* lm = io.lm + ((size_t)n * 4 + j) * NPIX;
-            const int pidx = lmy[j] * HWD + lmx[j];
+            const int pidx = lm_pixel(lmx[j], lmy[j]);
             for (int i = tid; i < NPIX; i += LOSS_THREADS) {
                 const float gt = (valid && i == pidx) ? 1.f : 0.f;
                 const float d = lm[i] - gt;
@@ -234,7 +239,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_kernel(const LossArgs a) {
                 if (io.lm_neg_idx) { io.lm_neg_idx[((size_t)j * N + n) * 2] = hard; io.lm_neg_idx[((size_t)j * N + n) * 2 + 1] = r; }
             }
             __syncthreads();
-            if (valid) {                                                // mask_gray_zone_lm (:1453-1462)
+            if (valid && pidx >= 0) {                                   // mask_gray_zone_lm (:1453-1462)
                 const Span sy = py_slice(lmy[j] - 2, lmy[j] + 3), sx = py_slice(lmx[j] - 2, lmx[j] + 3);
                 for (int i = tid; i < 25; i += LOSS_THREADS) {
                     const int y = sy.a + i / 5, x = sx.a + i % 5;
@@ -271,11 +276,11 @@ __global__ __launch_bounds__(LOSS_APPLY_THREADS) void loss_apply_kernel(const Lo
     const Box box = make_box(bb, valid);
     const float* score = io.score + (size_t)n * NPIX;
     const unsigned char* mb = a.maskbuf + (size_t)n * 5 * NPIX;
-    int lmx[4] = {0, 0, 0, 0}, lmy[4] = {0, 0, 0, 0};
+    int lmp[4] = {-1, -1, -1, -1};
     if (kind != 0) {
         const float* vt = io.vertices + 8 * n;
         const int clamp = a.d.use_labels;
-        for (int j = 0; j < 4; ++j) { lmx[j] = lm_coord(vt[2 * j], clamp); lmy[j] = lm_coord(vt[2 * j + 1], clamp); }
+        for (int j = 0; j < 4; ++j) lmp[j] = lm_pixel(lm_coord(vt[2 * j], clamp), lm_coord(vt[2 * j + 1], clamp));
     }
     const float l_loc = a.d.lambda_loc, l_det = (kind == 0) ? 1.f : a.d.lambda_det, l_lm = a.d.lambda_lm;
     double s_cls = 0, s_loc = 0, s_lm = 0, s_lmloc = 0, s_rf = 0;
@@ -306,7 +311,7 @@ __global__ __launch_bounds__(LOSS_APPLY_THREADS) void loss_apply_kernel(const Lo
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float ml = (float)mb[(1 + j) * NPIX + i];
-                const float hg = (valid && i == lmy[j] * HWD + lmx[j]) ? 1.f : 0.f;
+                const float hg = (valid && i == lmp[j]) ? 1.f : 0.f;
                 const size_t o = ((size_t)n * 4 + j) * NPIX + i;
                 const float dl = io.lm[o] - hg;
                 s_lm += (double)(ml * (dl * dl));
@@ -433,7 +438,7 @@ __global__ void init_lm_heatmap_kernel(const float* vert, const float* labels, i
         const int j = threadIdx.x;
         int x = lm_coord(vert[8 * n + 2 * j], clamp), y = lm_coord(vert[8 * n + 2 * j + 1], clamp);
         if (x >= HWD || y >= HWD) { if (err) atomicAdd(err, 1); x = min(x, HWD - 1); y = min(y, HWD - 1); }
-        out[((size_t)n * 4 + j) * NPIX + y * HWD + x] = 1.f;
+        if (x >= 0 && y >= 0) out[((size_t)n * 4 + j) * NPIX + y * HWD + x] = 1.f;      // a negative index is never used
     }
 }
 extern "C" int dbx_init_lm_heatmap(const float* vertices, const float* labels, int32_t n, int32_t clamp, float* out, void* stream) {

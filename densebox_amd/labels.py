@@ -2,7 +2,8 @@
 argument meaning (DenseBox.py:1368-1933).  Inputs may be CPU or GPU tensors; results are GPU
 tensors (fp32 NCHW like the reference's).  Every map is produced by a HIP kernel of
 libdensebox_hip.so; the only host arithmetic here is ``positive_count`` (integer bookkeeping
-the host needs to size the mining, identical to the kernel's -- cross-checked in tests)."""
+the host needs to size the mining, identical to the kernel's -- cross-checked in tests) and
+``check_landmarks`` (the IndexError of a landmark outside the grid, host-resident vertices only)."""
 import ctypes as C
 
 import numpy as np
@@ -80,11 +81,26 @@ def _heat(vertices, labels, clamp):
     return out
 
 
+def check_landmarks(vertices, labels=None, clamp=False):
+    """Raise IndexError when a landmark of a valid patch (``labels`` None or != 0) rounds -- int(v + 0.5), truncating; with ``clamp`` then
+    min(., 59) as init_lm_heatmap_pn -- outside [0, 60).  The reference raises from index 60 on and wraps -60..-1; this project refuses
+    both.  Host-resident vertices only: a device tensor is not read back and passes."""
+    v = torch.as_tensor(vertices)
+    if v.is_cuda:
+        return
+    idx = (v.detach().float().reshape(-1, 8) + 0.5).to(torch.int64)              # float32 add, truncation toward zero (int())
+    if clamp:
+        idx = idx.clamp(max=HW - 1)
+    bad = (idx < 0) | (idx >= HW)
+    if labels is not None:
+        bad &= (torch.as_tensor(labels).detach().cpu().float().reshape(-1, 1) != 0)
+    if bool(bad.any()):
+        raise IndexError('landmark index %d is out of bounds for dimension with size %d' % (int(idx[bad][0]), HW))
+
+
 def init_lm_heatmap(vertices, batch_size=None):
-    """DenseBox.py:1802-1825.  The reference raises IndexError when a landmark rounds to 60; so does this."""
-    v = torch.as_tensor(vertices).float()
-    if bool(((v + 0.5).to(torch.int64) >= HW).any()):
-        raise IndexError('landmark index 60 is out of bounds for dimension with size 60')
+    """DenseBox.py:1802-1825.  The reference raises IndexError when a landmark rounds to 60; so does this (and for a negative index)."""
+    check_landmarks(torch.as_tensor(vertices).cpu())
     return _heat(vertices, None, 0)
 
 

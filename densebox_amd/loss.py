@@ -39,7 +39,10 @@ def densebox_loss(kind, outputs, bbox, vertices=None, labels=None, rand_neg_indi
     ``np.random.choice`` draws of DenseBox.py:2089-2094 / :2133-2138; when None they are drawn here with
     ``rng`` (a numpy RandomState; default = numpy's global state, like the reference).
     batch_global / positive_num_global: data-parallel runs pass the global batch size and the all-reduced
-    positive count so every rank mines with the reference's global ``neg_num`` (DenseBox.py:2074)."""
+    positive count so every rank mines with the reference's global ``neg_num`` (DenseBox.py:2074).
+    A landmark of a valid patch whose rounded (for DenseBoxLMLOC: clamped) x or y is outside [0, 60) raises IndexError before anything
+    is launched when ``vertices`` are host-resident; device-resident vertices are not read back (no sync in the step): the kernel
+    never uses such a landmark as an index, its channel then has no positive pixel and no gray zone."""
     kid = _KIND_ID[kind]
     if kind == 'DenseBox':
         score, loc = outputs
@@ -51,8 +54,10 @@ def densebox_loss(kind, outputs, bbox, vertices=None, labels=None, rand_neg_indi
         score, rf, loc, lm, lmloc = outputs
     dev = score.device
     n = score.size(0)
-    assert tuple(score.shape[1:]) == (1, 60, 60), 'the dense loss is defined on the 60x60 training grid'
     use_labels = kind == 'DenseBoxLMLOC'
+    if kid != 0:
+        LB.check_landmarks(vertices, labels if use_labels else None, clamp=use_labels)
+    assert tuple(score.shape[1:]) == (1, 60, 60), 'the dense loss is defined on the 60x60 training grid'
     P = int(LB.positive_count(bbox, labels if use_labels else None).sum()) if positive_num_global is None \
         else int(positive_num_global)
     _, half = LB.neg_counts(P, n if batch_global is None else batch_global)
