@@ -34,6 +34,19 @@ class ConvPlan(C.Structure):
                 ('name', C.c_char * 64)]
 
 
+class Head2UpHalf(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ('px_lo', 'px_n', 'own_lo', 'own_hi', 'ix_lo', 'ix_n')]
+
+
+class Head2UpLaunch(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ('head0', 'heads', 'kj', 'groups', 'blocks')]
+
+
+class Head2UpPlan(C.Structure):
+    _fields_ = [('fused', C.c_int32), ('halves', C.c_int32), ('half', Head2UpHalf * 2), ('launches', C.c_int32),
+                ('launch', Head2UpLaunch * 4)]
+
+
 class LossDesc(C.Structure):
     _fields_ = [('kind', C.c_int32), ('n', C.c_int32), ('half_neg', C.c_int32),
                 ('lambda_loc', C.c_float), ('lambda_det', C.c_float), ('lambda_lm', C.c_float),
@@ -212,6 +225,7 @@ SIGNATURES = {
     'dbx_conv_wgrad_pool_dz_ok': (C.c_int, [_I32, _PV, _PV, _I32, _I32]),
     'dbx_conv_wgrad_pool_dz': (C.c_int, [_I32, _PV, _VP, _I32, _PV, _PV, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _I32, _I32, _VP]),
     'dbx_head2_backward_up_fused': (C.c_int, [_I32, _PV, _PV]),
+    'dbx_head2_backward_up_plan': (C.c_int, [_I32, _PV, _PV, C.POINTER(C.c_int32), _I32, C.POINTER(Head2UpPlan)]),
     'dbx_heads1_wgrad_gen_ok': (C.c_int, [_I32, _PV, _I32]),
     'dbx_heads1_dgrad_gen': (C.c_int, [_I32, _PV, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), _I32, _I32, C.c_uint32, _VP, _PV, _PV, _VP]),
     'dbx_heads1_wgrad_gen': (C.c_int, [_I32, _PV, _PV, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), _I32, _I32, C.c_uint32, _I32, _VP, _I32, _I32,

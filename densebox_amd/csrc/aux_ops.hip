@@ -1472,16 +1472,44 @@ static bool h2u_plan(int W, int ws, float sx, H2UPlan& p) {
     p.h[1] = H2UHalf{loR, W - loR, P, W, S, ws - S};
     return true;
 }
+// Does dbx_head2_backward_up run as ONE pass for these maps (element size esize)?  Fills the scales and, when it does, the row split.
+static bool h2u_fused(size_t esize, const dbx_view* hid, const dbx_view* dg, float& sy, float& sx, H2UPlan& plan) {
+    sy = ac_scale(dg->h, hid->h); sx = ac_scale(dg->w, hid->w);
+    bool fused = esize == 2 && sy > 0.f && sy < 1.f && sx > 0.45f && sx < 1.f && hid->c % 64 == 0 && hid->h >= 2 && h2u_plan(hid->w, dg->w, sx, plan);
+    if (const char* e = getenv("DBX_HEAD2_UP")) fused = fused && atoi(e) != 0;
+    return fused;
+}
+// The launches of the one-pass form: one per run of consecutive heads with the same k rounded up to 1 / 2 / 4 / 8 (round 4: the kernel
+// is VALU-bound -- ~250 instructions per row and wave with all eight d_out channels multiplied out -- and the heads have k = 1, 4, 4, 8:
+// the k = 1 launch runs 36 % fewer, the k = 4 launch 21 % fewer; DBX_HEAD2_UP_SPLIT=0, read once: one launch with eight channels).
+// Two workgroups per CU (248 VGPRs x 256 threads): `groups` workgroups per (channel slice, half), each walking every groups-th image.
+// dbx_head2_backward_up launches exactly what this returns and dbx_head2_backward_up_plan reports it.
+struct H2ULaunch { int h0, nhl, kj, groups, blocks; };                // first head, heads, KJ; blocks = groups * halves partial blocks
+static int h2u_launches(const int32_t* k, int nh, int n, int halves, H2ULaunch (&out)[4]) {
+    static int split = -1;
+    if (split < 0) { const char* e = getenv("DBX_HEAD2_UP_SPLIT"); split = e ? atoi(e) : 1; }
+    auto kup = [&](int kk) { return !split ? 8 : kk <= 1 ? 1 : kk <= 2 ? 2 : kk <= 4 ? 4 : 8; };
+    int nl = 0;
+    for (int h0 = 0; h0 < nh;) {
+        int h1 = h0 + 1;
+        while (h1 < nh && kup(k[h1]) == kup(k[h0])) ++h1;
+        const int nhl = h1 - h0, nsl = nhl * 8;
+        int groups = H2U_WGS / (nsl * halves);
+        groups = groups < 1 ? 1 : groups > n ? n : groups;
+        out[nl++] = H2ULaunch{h0, nhl, kup(k[h0]), groups, groups * halves};   // blocks <= 2 n <= n h: all launches together stay inside dbx_head2_wgrad_scratch_bytes
+        h0 = h1;
+    }
+    return nl;
+}
 template <typename T>
 static int head2_backward_up_t(const dbx_view* dout, const dbx_view* hid, const float* const* w2, const int32_t* k, int nh, const dbx_view* dhid,
                                const uint8_t* mask, int mask_ld, int use_hash, unsigned drop_seed, float* const* dw, float* const* db,
                                void* scratch, const dbx_view* dg, hipStream_t s) {
     VIEW_VEC_CHECK(T, dg, "head2_backward_up d_g44");
     DBX_REQUIRE(dg->n == hid->n && dg->c == hid->c, "head2_backward_up: d_g44 has the hidden map's batch and channels");
-    const float sy = ac_scale(dg->h, hid->h), sx = ac_scale(dg->w, hid->w);
+    float sy, sx;
     H2UPlan plan;
-    bool fused = sizeof(T) == 2 && sy > 0.f && sy < 1.f && sx > 0.45f && sx < 1.f && hid->c % 64 == 0 && hid->h >= 2 && h2u_plan(hid->w, dg->w, sx, plan);
-    if (const char* e = getenv("DBX_HEAD2_UP")) fused = fused && atoi(e) != 0;
+    const bool fused = h2u_fused(sizeof(T), hid, dg, sy, sx, plan);
     const bool nostore = dhid->ptr == nullptr;                          // the hidden gradient is not wanted in memory (its consumers generate it)
     DBX_REQUIRE(!nostore || (fused && !mask), "head2_backward_up without d_hid: needs the one-pass kernel (dbx_head2_backward_up_fused) and hash / no dropout");
     if (!fused) {                                                       // the two passes
@@ -1504,10 +1532,6 @@ static int head2_backward_up_t(const dbx_view* dout, const dbx_view* hid, const 
             ha.w2[i] = i < nh ? w2[i] : nullptr; ha.k[i] = i < nh ? k[i] : 0;
             if (i < nh) DBX_REQUIRE(k[i] >= 1 && k[i] <= 8 && dw[i] && w2[i] && ((size_t)w2[i] % 16) == 0, "head2_backward_up: k in 1..8, 16-byte aligned weights");
         }
-        // One launch per run of consecutive heads with the same k rounded up to 1 / 2 / 4 / 8 (round 4: the kernel is VALU-bound --
-        // ~250 instructions per row and wave with all eight d_out channels multiplied out -- and the heads have k = 1, 4, 4, 8: the
-        // k = 1 launch runs 36 % fewer, the k = 4 launch 21 % fewer; DBX_HEAD2_UP_SPLIT=0: one launch with eight channels).
-        // Two workgroups per CU (248 VGPRs x 256 threads): `groups` workgroups per (channel slice, half), each walking every groups-th image.
         constexpr size_t smem = (size_t)2 * H2U_NB * 32 * 64 * 4;       // the ring (>= the 4 x 8 x 64 + 32 floats of the final reduction)
         static_assert(smem >= (4 * 8 * 64 + 32) * 4 && 2 * smem + 4096 <= 160 * 1024, "LDS budget of two workgroups per CU");
         static DbxDevOnce attr_once; int attr_dev = 0;
@@ -1518,19 +1542,13 @@ static int head2_backward_up_t(const dbx_view* dout, const dbx_view* hid, const 
             DBX_HIP(hipFuncSetAttribute((const void*)head2_backward_up_kernel<T, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
             attr_once.mark(attr_dev);
         }
-        static int split = -1;
-        if (split < 0) { const char* e = getenv("DBX_HEAD2_UP_SPLIT"); split = e ? atoi(e) : 1; }
-        auto kup = [&](int kk) { return !split ? 8 : kk <= 1 ? 1 : kk <= 2 ? 2 : kk <= 4 ? 4 : 8; };
+        H2ULaunch launches[4];
+        const int nl = h2u_launches(k, nh, hid->n, plan.halves, launches);
         float* const pbase = (float*)scratch;
         long long pused = 0;                                            // floats of the scratch handed out
         int blocks_max = 0;
-        for (int h0 = 0; h0 < nh;) {
-            int h1 = h0 + 1;
-            while (h1 < nh && kup(k[h1]) == kup(k[h0])) ++h1;
-            const int nhl = h1 - h0, nsl = nhl * 8, kj = kup(k[h0]);
-            int groups = H2U_WGS / (nsl * plan.halves);
-            groups = groups < 1 ? 1 : groups > hid->n ? hid->n : groups;
-            const int blocks = groups * plan.halves;                    // <= 2 n <= n h: all launches together stay inside dbx_head2_wgrad_scratch_bytes
+        for (int li = 0; li < nl; ++li) {
+            const int h0 = launches[li].h0, nhl = launches[li].nhl, h1 = h0 + nhl, nsl = nhl * 8, kj = launches[li].kj, blocks = launches[li].blocks;
             float* partial = pbase + pused;
             float* bpartial = partial + (size_t)blocks * nhl * 8 * 512;
             for (int i = h0; i < h1; ++i) { o.poff[i] = pused; o.boff[i] = pused + (long long)blocks * nhl * 8 * 512; o.nblk[i] = blocks; o.nhl[i] = nhl; o.hl[i] = i - h0; }
@@ -1543,7 +1561,6 @@ static int head2_backward_up_t(const dbx_view* dout, const dbx_view* hid, const 
             if (kj == 1) H2U_LAUNCH(1); else if (kj == 2) H2U_LAUNCH(2); else if (kj == 4) H2U_LAUNCH(4); else H2U_LAUNCH(8);
 #undef H2U_LAUNCH
             DBX_LAUNCH_CHECK();
-            h0 = h1;
         }
         for (int i = nh; i < 4; ++i) { o.poff[i] = 0; o.boff[i] = 0; o.nblk[i] = 0; o.nhl[i] = 1; o.hl[i] = 0; }
         float* partial = pbase; float* bpartial = pbase;                // (the reduction takes each head's offsets from o)
@@ -1556,15 +1573,39 @@ static int head2_backward_up_t(const dbx_view* dout, const dbx_view* hid, const 
 }
 // 1 when dbx_head2_backward_up runs as ONE pass for these maps (the form that can leave d_hid out: d_hid->ptr == NULL)
 template <typename T> static int head2_up_fused_t(const dbx_view* hid, const dbx_view* dg) {
-    const float sy = ac_scale(dg->h, hid->h), sx = ac_scale(dg->w, hid->w);
+    float sy, sx;
     H2UPlan plan;
-    bool fused = sizeof(T) == 2 && sy > 0.f && sy < 1.f && sx > 0.45f && sx < 1.f && hid->c % 64 == 0 && hid->h >= 2 && h2u_plan(hid->w, dg->w, sx, plan);
-    if (const char* e = getenv("DBX_HEAD2_UP")) fused = fused && atoi(e) != 0;
-    return fused ? 1 : 0;
+    return h2u_fused(sizeof(T), hid, dg, sy, sx, plan) ? 1 : 0;
 }
 extern "C" int dbx_head2_backward_up_fused(int32_t dtype, const dbx_view* hid, const dbx_view* d_g44) {
     if (!hid || !d_g44) return 0;
     switch (dtype) { case DBX_F16: return head2_up_fused_t<_Float16>(hid, d_g44); case DBX_BF16: return head2_up_fused_t<__bf16>(hid, d_g44); default: return 0; }
+}
+// What dbx_head2_backward_up would launch for these maps and heads (host only: nothing is launched, no pointer is followed).
+extern "C" int dbx_head2_backward_up_plan(int32_t dtype, const dbx_view* hid, const dbx_view* d_g44, const int32_t* k, int32_t nh,
+                                          dbx_head2_up_plan_t* out) {
+    if (!hid || !d_g44 || !k || !out) { dbx_set_error("head2_backward_up_plan: null argument"); return DBX_ERR_ARG; }
+    if (dtype != DBX_F16 && dtype != DBX_BF16 && dtype != DBX_F32) { dbx_set_error("head2_backward_up_plan: unknown dtype"); return DBX_ERR_DTYPE; }
+    DBX_REQUIRE(nh >= 1 && nh <= 4 && hid->c == 512 * nh && d_g44->n == hid->n && d_g44->c == hid->c,
+                "head2_backward_up_plan: nh in 1..4, hid of 512*nh channels, d_g44 with the hidden map's batch and channels");
+    for (int i = 0; i < nh; ++i) DBX_REQUIRE(k[i] >= 1 && k[i] <= 8, "head2_backward_up_plan: k in 1..8");
+    *out = dbx_head2_up_plan_t{};
+    float sy, sx;
+    H2UPlan plan;
+    if (!h2u_fused(dtype == DBX_F32 ? 4 : 2, hid, d_g44, sy, sx, plan)) return DBX_OK;      // the two passes: fused 0, no launches listed
+    out->fused = 1; out->halves = plan.halves;
+    for (int i = 0; i < 2; ++i) {
+        const H2UHalf& h = plan.h[i];
+        out->half[i].px_lo = h.px_lo; out->half[i].px_n = h.px_n; out->half[i].own_lo = h.own_lo; out->half[i].own_hi = h.own_hi;
+        out->half[i].ix_lo = h.ix_lo; out->half[i].ix_n = h.ix_n;
+    }
+    H2ULaunch l[4];
+    out->launches = h2u_launches(k, nh, hid->n, plan.halves, l);
+    for (int i = 0; i < out->launches; ++i) {
+        out->launch[i].head0 = l[i].h0; out->launch[i].heads = l[i].nhl; out->launch[i].kj = l[i].kj; out->launch[i].groups = l[i].groups;
+        out->launch[i].blocks = l[i].blocks;
+    }
+    return DBX_OK;
 }
 extern "C" int dbx_head2_backward_up(int32_t dtype, const dbx_view* d_out, const dbx_view* hid, const float* const* w2, const int32_t* k,
                                      int32_t nh, const dbx_view* d_hid, const uint8_t* dropmask, int32_t dropmask_ld, int32_t use_hash,

@@ -68,7 +68,9 @@ const char* dbx_last_error(void);
  *      also at 13, without a bump: dbx_overlay_frame, dbx_overlay_style, dbx_draw_overlay_batch, dbx_overlay_font, dbx_overlay_label
  *      (annotated frames painted on the device), pure additions likewise
  *      also at 13, without a bump: dbx_patch_job, dbx_patch_geom, dbx_patch_plan_io, dbx_patch_plan, dbx_patch_cut, dbx_patch_plan_host,
- *      dbx_patch_draw, dbx_patch_check_tables (training patches sampled and cut on the device), pure additions likewise */
+ *      dbx_patch_draw, dbx_patch_check_tables (training patches sampled and cut on the device), pure additions likewise
+ *      also at 13, without a bump: dbx_head2_up_plan_t, dbx_head2_backward_up_plan (which launches dbx_head2_backward_up makes: a
+ *      read-only host query), a pure addition likewise */
 #define DBX_ABI_VERSION 13
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
@@ -269,6 +271,26 @@ int dbx_conv_wgrad_pool_dz(int32_t dtype, const dbx_view* dy, const void* idx, i
  * width >= k, x / y / gate any frames, w1t_frag is the PLAIN dbx_pack_weight mode 1 image (rows of 512 nh floats) and scratch is unused.
  * (Heads: DenseBox.py:158-162, :174-178; their backward is autograd's in the reference.) */
 int dbx_head2_backward_up_fused(int32_t dtype, const dbx_view* hid, const dbx_view* d_g44);
+/* What dbx_head2_backward_up would run for (dtype, hid, d_g44, k[0 .. nh)): a read-only query on the host -- nothing is launched, no
+ * view's ptr is followed -- computed by the helpers the entry point itself dispatches through (the tests of the stage-2 backward
+ * assert from it which path a case takes).  fused 0: the two passes (dbx_head2_backward, then dbx_upsample_bilinear_bwd); every other
+ * field is 0.  fused 1: `halves` workgroups share a row of the hidden map, half[i] walks its pixel columns [px_lo, px_lo + px_n),
+ * stores and accumulates the columns [own_lo, own_hi) and reduces d_g44's columns [ix_lo, ix_lo + ix_n) (halves 1: half[1] repeats
+ * half[0]); launch[0 .. launches) are the kernel launches in order: heads [head0, head0 + heads) with kj of their d_out channels
+ * multiplied out (k rounded up to 1 / 2 / 4 / 8), `groups` workgroups per (64-channel slice, half) -- workgroup g walks the images g,
+ * g + groups, ... -- and blocks = groups * halves partial weight-gradient blocks (the launch's grid is blocks * 8 * heads workgroups).
+ * Layouts: dbx_head2_up_half 24 bytes (px_lo 0, px_n 4, own_lo 8, own_hi 12, ix_lo 16, ix_n 20); dbx_head2_up_launch 20 bytes (head0 0,
+ * heads 4, kj 8, groups 12, blocks 16); dbx_head2_up_plan_t 140 bytes (fused 0, halves 4, half 8, launches 56, launch 60). */
+typedef struct dbx_head2_up_half { int32_t px_lo, px_n, own_lo, own_hi, ix_lo, ix_n; } dbx_head2_up_half;
+typedef struct dbx_head2_up_launch { int32_t head0, heads, kj, groups, blocks; } dbx_head2_up_launch;
+typedef struct dbx_head2_up_plan_t {
+    int32_t fused, halves;
+    dbx_head2_up_half half[2];
+    int32_t launches;
+    dbx_head2_up_launch launch[4];
+} dbx_head2_up_plan_t;
+int dbx_head2_backward_up_plan(int32_t dtype, const dbx_view* hid, const dbx_view* d_g44, const int32_t* k, int32_t nh,
+                               dbx_head2_up_plan_t* out);
 int dbx_heads1_wgrad_gen_ok(int32_t dtype, const dbx_view* x, int32_t nh);
 int dbx_heads1_wgrad_gen(int32_t dtype, const dbx_view* d_out, const dbx_view* x, const float* const* w2, const int32_t* k, int32_t nh,
                          int32_t use_hash, uint32_t drop_seed, int32_t ci, float* dw_oihw, int32_t dw_ci_total, int32_t dw_ci_off,

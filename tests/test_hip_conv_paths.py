@@ -55,6 +55,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import conv_ref as R                                    # noqa: E402
+from heads_ref import drop_keep                         # noqa: E402  (dbx_drop_hash32 restated; shared with the heads backward's reference)
 
 from densebox_amd import _lib                           # noqa: E402
 from densebox_amd._lib import View, ConvDesc, check, ptr, stream_ptr   # noqa: E402
@@ -345,22 +346,6 @@ def operands(c):
         shape_w = (c.ci, c.co) if tr else (c.co, c.ci)
         _OPS[key] = R.int_operands(seed, c.n, c.ci, shape_w[0], shape_w[1], c.k, c.h, c.w, c.q, c.ho, c.wo, c.co) + ({},)
     return _OPS[key]
-
-
-def drop_keep(seed, M, co):
-    """dbx_drop_hash32 (csrc/common.hpp) restated: keep bit of (pixel m, channel ch) = bit ch % 32 of a lowbias32 finaliser over
-    (seed, m, ch / 32).  Returns bool [M][co]."""
-    m = np.arange(M, dtype=np.uint64)[:, None]
-    c32 = (np.arange(co, dtype=np.uint64) // np.uint64(32))[None, :]
-    mask = np.uint64(0xFFFFFFFF)
-    x = (np.uint64(seed) ^ ((m * np.uint64(0x9E3779B1)) & mask) ^ ((c32 * np.uint64(0x85EBCA77)) & mask)) & mask
-    x ^= x >> np.uint64(16)
-    x = (x * np.uint64(0x7FEB352D)) & mask
-    x ^= x >> np.uint64(15)
-    x = (x * np.uint64(0x846CA68B)) & mask
-    x ^= x >> np.uint64(16)
-    bit = (np.arange(co, dtype=np.uint64) % np.uint64(32))[None, :]
-    return ((x >> bit) & np.uint64(1)).astype(bool)
 
 
 def epilogue64(c, pre, gate):
