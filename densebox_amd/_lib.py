@@ -47,6 +47,10 @@ class Head2UpPlan(C.Structure):
                 ('launch', Head2UpLaunch * 4)]
 
 
+class UpsampleBwdPlan(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ('kernel', 'nseg', 'workgroups', 'lds_bytes')]
+
+
 class LossDesc(C.Structure):
     _fields_ = [('kind', C.c_int32), ('n', C.c_int32), ('half_neg', C.c_int32),
                 ('lambda_loc', C.c_float), ('lambda_det', C.c_float), ('lambda_lm', C.c_float),
@@ -244,6 +248,7 @@ SIGNATURES = {
     'dbx_maxpool2x2_bwd_idx': (C.c_int, [_I32, _VP, _PV, _PV, _I32, _I32, _VP]),
     'dbx_upsample_bilinear': (C.c_int, [_I32, _PV, _PV, _VP]),
     'dbx_upsample_bilinear_bwd': (C.c_int, [_I32, _PV, _PV, _PV, _VP]),
+    'dbx_upsample_bilinear_bwd_plan': (C.c_int, [_I32, _PV, _PV, C.POINTER(UpsampleBwdPlan)]),
     'dbx_loss_scratch_bytes': (C.c_int64, [_I32]),
     'dbx_loss_forward_backward': (C.c_int, [C.POINTER(LossDesc), C.POINTER(LossIO), _VP, _VP]),
     'dbx_count_positives': (C.c_int, [_VP, _VP, _I32, _VP, _VP]),

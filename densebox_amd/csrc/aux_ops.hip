@@ -370,31 +370,6 @@ __device__ __forceinline__ void bilin_coef(int d, float scale, int in, int& i0, 
 static inline float ac_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 
 template <typename T>
-__global__ void upsample_kernel(FrameGeo x, FrameGeo y, float sy, float sx) {
-    constexpr int V = Vec<T>::N;
-    const int cg = y.c / V;
-    const int64_t total = (int64_t)y.n * y.h * y.w * cg;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int g = (int)(i % cg);
-        const int px = (int)((i / cg) % y.w);
-        const int py = (int)((i / ((int64_t)cg * y.w)) % y.h);
-        const int n = (int)(i / ((int64_t)cg * y.w * y.h));
-        int y0, y1, x0, x1;
-        float ly0, ly1, lx0, lx1;
-        bilin_coef(py, sy, x.h, y0, y1, ly0, ly1);
-        bilin_coef(px, sx, x.w, x0, x1, lx0, lx1);
-        float a[V], b[V], c[V], d[V], o[V];
-        const T* base = (const T*)x.base + g * V;
-        load_vec<T>(base + geo_pix(x, n, y0, x0), a);
-        load_vec<T>(base + geo_pix(x, n, y0, x1), b);
-        load_vec<T>(base + geo_pix(x, n, y1, x0), c);
-        load_vec<T>(base + geo_pix(x, n, y1, x1), d);
-#pragma unroll
-        for (int j = 0; j < V; ++j) o[j] = ly0 * (lx0 * a[j] + lx1 * b[j]) + ly1 * (lx0 * c[j] + lx1 * d[j]);
-        store_vec<T>((T*)y.base + geo_pix(y, n, py, px) + g * V, o);
-    }
-}
-template <typename T>
 __global__ __launch_bounds__(256) void upsample_rows_kernel(FrameGeo x, FrameGeo y, float sy, float sx) {
     constexpr int V = Vec<T>::N;
     const int cg = y.c / V;
@@ -693,36 +668,73 @@ __global__ __launch_bounds__(256, 4) void upsample_bwd_walk_kernel(FrameGeo dy, 
     }
 }
 
+// Which backward kernel a pair of maps takes, and its launch: ONE rule, used by upsample_bwd_t and reported by
+// dbx_upsample_bilinear_bwd_plan (host only).  esize: bytes per element (16 / esize channels per lane).
+struct UpBwdPlan { int kernel, nseg, pairs, workgroups, lds_bytes; float sy, sx; };      // kernel: 0 flat, 1 rows, 2 walk
+static UpBwdPlan upsample_bwd_plan(size_t esize, const dbx_view* dy, const dbx_view* dx) {
+    UpBwdPlan p{};
+    const int cg = dx->c / (int)(16 / esize);
+    p.sy = ac_scale(dx->h, dy->h); p.sx = ac_scale(dx->w, dy->w);
+    const float sy = p.sy, sx = p.sx;
+    // up-sampling by ~2 (every destination column interpolates from x0 and x0 + 1 with x0 non-decreasing, <= 8 destination rows per
+    // source-row pair) on maps with >= 64 channel groups: the column walk.  It keeps the element offsets of dy's rows in 32 bits, so
+    // the framed dy must span fewer than 2^32 elements (a larger map takes the tabulated kernel, whose offsets are size_t)
+    const uint64_t dy_span = (uint64_t)dy->n * (uint64_t)(dy->h + 2 * dy->pad) * (uint64_t)(dy->w + 2 * dy->pad) * (uint64_t)dy->ld;
+    const bool walk_ok = sy > 0.45f && sy < 1.f && sx > 0.45f && sx < 1.f && cg >= 64 && dy->w <= 4096 && dy_span < (1ull << 32);
+    // the tabulated kernel covers up-sampling factors up to ~3 (<= 8 destination columns and <= 16 rows per source pixel); its
+    // table (36 B per source column) stays inside the 64 KB of dynamic LDS a launch gets without an attribute
+    const bool rows_ok = sy > 0.34f && sx > 0.34f && dx->w <= 1536;
+    if (walk_ok) {
+        p.kernel = 2;
+        p.pairs = (dx->h + 1) / 2;
+        // enough workgroups for ~12 waves per SIMD over the channel-group rounds of a thread (at most one segment per 8 source columns)
+        const int rounds = (cg + 255) / 256;
+        int nseg = (int)(12288 / ((int64_t)dx->n * p.pairs * 4 * rounds) + 1);
+        if (nseg > dx->w / 8) nseg = dx->w / 8;
+        if (nseg < 1) nseg = 1;
+        p.nseg = nseg;
+        p.workgroups = dx->n * p.pairs * nseg;
+        p.lds_bytes = dy->w * 12;
+    } else if (rows_ok) {
+        p.kernel = 1;
+        p.workgroups = dx->n * dx->h;
+        p.lds_bytes = dx->w * (4 + 8 * 4);
+    } else {
+        p.kernel = 0;
+        p.workgroups = grid_for((int64_t)dx->n * dx->h * dx->w * cg);
+    }
+    return p;
+}
 template <typename T>
 static int upsample_bwd_t(const dbx_view* dy, const dbx_view* dx, const dbx_view* gate, hipStream_t s) {
     VIEW_VEC_CHECK(T, dy, "upsample_bwd dy"); VIEW_VEC_CHECK(T, dx, "upsample_bwd dx");
     DBX_REQUIRE(dx->c == dy->c && dx->n == dy->n, "upsample_bwd: channel/batch mismatch");
     if (gate) { VIEW_VEC_CHECK(T, gate, "upsample_bwd gate"); DBX_REQUIRE(gate->h == dx->h && gate->w == dx->w && gate->c == dx->c, "upsample_bwd: gate shape"); }
-    const int64_t total = (int64_t)dx->n * dx->h * dx->w * (dx->c / Vec<T>::N);
     FrameGeo gg = gate ? make_geo<T>(gate) : make_geo<T>(dx);
-    const float sy = ac_scale(dx->h, dy->h), sx = ac_scale(dx->w, dy->w);
-    // up-sampling by ~2 (every destination column interpolates from x0 and x0 + 1 with x0 non-decreasing, <= 8 destination rows per
-    // source-row pair) on maps with >= 64 channel groups: the column walk
-    const bool walk_ok = sy > 0.45f && sy < 1.f && sx > 0.45f && sx < 1.f && dx->c / Vec<T>::N >= 64 && dy->w <= 4096;
-    // the tabulated kernel covers up-sampling factors up to ~3 (<= 8 destination columns and <= 16 rows per source pixel); its
-    // table (36 B per source column) stays inside the 64 KB of dynamic LDS a launch gets without an attribute
-    const bool rows_ok = sy > 0.34f && sx > 0.34f && dx->w <= 1536;
-    if (walk_ok) {
-        const int pairs = (dx->h + 1) / 2;
-        // enough workgroups for ~12 waves per SIMD over the channel-group rounds of a thread (at most one segment per 8 source columns)
-        const int rounds = (dx->c / Vec<T>::N + 255) / 256;
-        int nseg = (int)(12288 / ((int64_t)dx->n * pairs * 4 * rounds) + 1);
-        if (nseg > dx->w / 8) nseg = dx->w / 8;
-        if (nseg < 1) nseg = 1;
-        hipLaunchKernelGGL(upsample_bwd_walk_kernel<T>, dim3(dx->n * pairs * nseg), dim3(256), (size_t)dy->w * 12, s, make_geo<T>(dy), make_geo<T>(dx), gg,
-                           gate ? 1 : 0, sy, sx, pairs, nseg);
-    } else if (rows_ok)
-        hipLaunchKernelGGL(upsample_bwd_rows_kernel<T>, dim3(dx->n * dx->h), dim3(256), (size_t)dx->w * (4 + 8 * 4), s, make_geo<T>(dy), make_geo<T>(dx), gg,
-                           gate ? 1 : 0, sy, sx);
+    const UpBwdPlan p = upsample_bwd_plan(sizeof(T), dy, dx);
+    if (p.kernel == 2)
+        hipLaunchKernelGGL(upsample_bwd_walk_kernel<T>, dim3(p.workgroups), dim3(256), (size_t)p.lds_bytes, s, make_geo<T>(dy), make_geo<T>(dx), gg,
+                           gate ? 1 : 0, p.sy, p.sx, p.pairs, p.nseg);
+    else if (p.kernel == 1)
+        hipLaunchKernelGGL(upsample_bwd_rows_kernel<T>, dim3(p.workgroups), dim3(256), (size_t)p.lds_bytes, s, make_geo<T>(dy), make_geo<T>(dx), gg,
+                           gate ? 1 : 0, p.sy, p.sx);
     else
-        hipLaunchKernelGGL(upsample_bwd_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, make_geo<T>(dy), make_geo<T>(dx), gg,
-                           gate ? 1 : 0, sy, sx);
+        hipLaunchKernelGGL(upsample_bwd_kernel<T>, dim3(p.workgroups), dim3(256), 0, s, make_geo<T>(dy), make_geo<T>(dx), gg,
+                           gate ? 1 : 0, p.sy, p.sx);
     DBX_LAUNCH_CHECK();
+    return DBX_OK;
+}
+// What dbx_upsample_bilinear_bwd would launch for these maps (host only: nothing is launched, no pointer is followed).
+extern "C" int dbx_upsample_bilinear_bwd_plan(int32_t dtype, const dbx_view* dy, const dbx_view* dx, dbx_upsample_bwd_plan_t* out) {
+    if (!dy || !dx || !out) { dbx_set_error("upsample_bilinear_bwd_plan: null argument"); return DBX_ERR_ARG; }
+    if (dtype != DBX_F16 && dtype != DBX_BF16 && dtype != DBX_F32) { dbx_set_error("upsample_bilinear_bwd_plan: unknown dtype"); return DBX_ERR_DTYPE; }
+    const size_t esize = dtype == DBX_F32 ? 4 : 2;
+    DBX_REQUIRE(dx->c == dy->c && dx->n == dy->n && dx->c >= 1 && (dx->c * esize) % 16 == 0 && dx->n >= 1 && dx->h >= 1 && dx->w >= 1 &&
+                    dy->h >= 1 && dy->w >= 1,
+                "upsample_bilinear_bwd_plan: dy and dx of one batch and channel count (a multiple of 16 bytes), every extent >= 1");
+    const UpBwdPlan p = upsample_bwd_plan(esize, dy, dx);
+    *out = dbx_upsample_bwd_plan_t{};
+    out->kernel = p.kernel; out->nseg = p.nseg; out->workgroups = p.workgroups; out->lds_bytes = p.lds_bytes;
     return DBX_OK;
 }
 extern "C" int dbx_upsample_bilinear_bwd(int32_t dtype, const dbx_view* dy, const dbx_view* dx, const dbx_view* gate, void* stream) {

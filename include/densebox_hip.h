@@ -70,7 +70,9 @@ const char* dbx_last_error(void);
  *      also at 13, without a bump: dbx_patch_job, dbx_patch_geom, dbx_patch_plan_io, dbx_patch_plan, dbx_patch_cut, dbx_patch_plan_host,
  *      dbx_patch_draw, dbx_patch_check_tables (training patches sampled and cut on the device), pure additions likewise
  *      also at 13, without a bump: dbx_head2_up_plan_t, dbx_head2_backward_up_plan (which launches dbx_head2_backward_up makes: a
- *      read-only host query), a pure addition likewise */
+ *      read-only host query), a pure addition likewise
+ *      also at 13, without a bump: dbx_upsample_bwd_plan_t, dbx_upsample_bilinear_bwd_plan (which kernel dbx_upsample_bilinear_bwd
+ *      launches: a read-only host query), a pure addition likewise */
 #define DBX_ABI_VERSION 13
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
@@ -404,6 +406,16 @@ int dbx_maxpool2x2_bwd_idx(int32_t dtype, const void* idx, const dbx_view* dy, c
 int dbx_upsample_bilinear(int32_t dtype, const dbx_view* x, const dbx_view* y, void* stream);
 /* gate (optional): forward activation of dx's tensor; dx is zeroed where gate <= 0 (ReLU backward) */
 int dbx_upsample_bilinear_bwd(int32_t dtype, const dbx_view* dy, const dbx_view* dx, const dbx_view* gate, void* stream);
+/* What dbx_upsample_bilinear_bwd would run for (dtype, dy, dx): a read-only query on the host -- nothing is launched, no view's ptr is
+ * followed -- computed by the helper the entry point itself dispatches through (tests/test_hip_aux_paths.py asserts from it which
+ * path a case takes).  kernel: 0 the flat gather (one lane per source pixel and 16-byte channel group: any geometry), 1 the tabulated
+ * rows kernel (one workgroup per source row; both scales above 0.34 and dx at most 1536 wide), 2 the column walk (one workgroup per
+ * pair of source rows and segment of source columns; both scales in (0.45, 1), at least 64 channel groups, dy at most 4096 wide and
+ * its frame spanning fewer than 2^32 elements).  nseg: column segments per row pair (walk only, else 0); workgroups: the launch's
+ * grid; lds_bytes: the dynamic LDS it asks for.  Layout: dbx_upsample_bwd_plan_t 16 bytes (kernel 0, nseg 4, workgroups 8,
+ * lds_bytes 12). */
+typedef struct dbx_upsample_bwd_plan_t { int32_t kernel, nseg, workgroups, lds_bytes; } dbx_upsample_bwd_plan_t;
+int dbx_upsample_bilinear_bwd_plan(int32_t dtype, const dbx_view* dy, const dbx_view* dx, dbx_upsample_bwd_plan_t* out);
 
 /* ------------------------------------------------------------------ dense per-pixel loss (DenseBox.py:2023-2180 etc.)
  * One call builds the label maps (a5-a8), element-wise L2, hard-negative mining (top-k per sample),

@@ -152,9 +152,10 @@ def max_terms(case):
     return int((up_matrix(case.h, case.hs) != 0).sum(axis=0).max() * (up_matrix(case.w, case.ws) != 0).sum(axis=0).max())
 
 
-def interval(g44, g44_abs, dtn):
-    """(d): the closed interval of T values a kernel's d_g44 may take, and the share of outputs where it holds more than one."""
-    E = 16 * 2.0 ** -24 * g44_abs
+def interval(g44, g44_abs, dtn, K=16):
+    """(d): the closed interval of T values a kernel's d_g44 may take, and the share of outputs where it holds more than one.  K: the
+    roundings a term passes through (16 here; tests/aux_ref.py derives its kernels' own)."""
+    E = K * 2.0 ** -24 * g44_abs
     lo, hi = round_np(g44 - E, dtn), round_np(g44 + E, dtn)
     return lo, hi, float((lo != hi).mean())
 

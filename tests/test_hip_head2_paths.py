@@ -43,6 +43,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import heads_ref as R                                   # noqa: E402
+from framed_buf import Buf, assert_holds                # noqa: E402
 
 from densebox_amd import _lib                           # noqa: E402
 from densebox_amd._lib import View, check, stream_ptr   # noqa: E402
@@ -54,69 +55,6 @@ if 'DBX_HEAD2_UP' in os.environ or 'DBX_HEAD2_UP_SPLIT' in os.environ:
 TDT = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32}
 SENTINEL, FILL, SLOT, TAIL = 1000.0, 7.0, 16, 4096          # 1000 and 7 are exact in bf16, f16 and fp32
 DROPS = ['none', 'hash', 'mask']
-
-
-class Buf:
-    """A framed NHWC buffer (or, with h = w = 1 and pad 0, a plain array of n rows) between two guard bands: `exp` is what it must hold,
-    `dev` the device copy, made by upload()."""
-
-    def __init__(self, name, n, h, w, pad, ld, tdt, fill, interior=None):
-        self.name, self.shape, self.pad, self.ld, self.tdt = name, (n, h, w), pad, ld, tdt
-        hp, wp = h + 2 * pad, w + 2 * pad
-        self.guard = -(-max(2 * wp * ld, 64) // 64) * 64
-        a = np.full(2 * self.guard + n * hp * wp * ld, fill, dtype=np.float64)
-        self.body = a[self.guard:self.guard + n * hp * wp * ld].reshape(n, hp, wp, ld)
-        if interior is not None:
-            self.body[:, pad:pad + h, pad:pad + w] = interior
-        self.np = a
-        self.dev = None
-
-    def tensor(self, a=None):
-        return torch.from_numpy(self.np if a is None else a).to(self.tdt)           # (every value is representable: the cast is exact)
-
-    def with_interior(self, interior):
-        n, h, w = self.shape
-        a = self.np.copy()
-        a[self.guard:self.guard + self.body.size].reshape(self.body.shape)[:, self.pad:self.pad + h, self.pad:self.pad + w] = interior
-        return self.tensor(a)
-
-    def upload(self):
-        self.dev = self.tensor().cuda()
-        return self
-
-    def ptr(self):
-        return self.dev.data_ptr() + self.guard * self.dev.element_size()
-
-    def view(self, c=None, null=False):
-        n, h, w = self.shape
-        return View(None if null else C.c_void_p(self.ptr()), n, h, w, self.pad, self.ld, 0, c or self.ld)
-
-    def where(self, i):
-        """Flat index -> a readable place."""
-        if i < self.guard or i >= self.guard + self.body.size:
-            return 'guard band (flat index %d, body at [%d, %d))' % (i, self.guard, self.guard + self.body.size)
-        n, hp, wp, ld = self.body.shape
-        j = i - self.guard
-        img, y, x, c = j // (hp * wp * ld), j // (wp * ld) % hp - self.pad, j // ld % wp - self.pad, j % ld
-        halo = not (0 <= y < self.shape[1] and 0 <= x < self.shape[2])
-        return '%simage %d row %d column %d channel %d (head %d, channel %d)' % ('HALO ' if halo else '', img, y, x, c, c // 512, c % 512)
-
-
-def assert_holds(buf, want=None, lo=None, hi=None, what=''):
-    """The device buffer equals `want` (default: what it was created with) everywhere, or lies in [lo, hi] everywhere."""
-    got = buf.dev.cpu()
-    if lo is None:
-        want = buf.tensor() if want is None else want
-        bad = got != want
-    else:
-        bad = ~((got >= lo) & (got <= hi))
-        want = lo
-    if bool(bad.any()):
-        idx = torch.nonzero(bad.flatten())[:, 0]
-        i = int(idx[0])
-        raise AssertionError('%s %s: %d of %d elements differ, the first at %s: got %r, want %r%s' % (
-            what, buf.name, idx.numel(), got.numel(), buf.where(i), float(got.flatten()[i]), float(want.flatten()[i]),
-            '' if hi is None else ' .. %r' % float(hi.flatten()[i])))
 
 
 class Call:
