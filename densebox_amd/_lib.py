@@ -148,6 +148,23 @@ class PatchAugIO(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ('labels_in', 'count', 'params_in', 'state', 'params', 'labels', 'bbox', 'vertices', 'label')]
 
 
+class PatchWarpRec(C.Structure):
+    _fields_ = [('flags', C.c_int32), ('border', C.c_int32), ('fill', C.c_int32), ('rot', C.c_int32), ('quad', C.c_int32 * 8),
+                ('scale', C.c_int32), ('aspect', C.c_int32), ('shear', C.c_int32), ('reserved', C.c_int32)]
+
+
+class PatchWarpCfg(C.Structure):
+    _fields_ = [('p_warp', C.c_double), ('rot_lo', C.c_int32), ('rot_hi', C.c_int32), ('scale_lo', C.c_int32), ('scale_hi', C.c_int32),
+                ('aspect_lo', C.c_int32), ('aspect_hi', C.c_int32), ('shear_lo', C.c_int32), ('shear_hi', C.c_int32), ('tx', C.c_int32),
+                ('ty', C.c_int32), ('jitter', C.c_int32), ('margin', C.c_int32), ('border', C.c_int32), ('fill', C.c_int32), ('R', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
+class PatchWarpIO(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ('labels_in', 'count', 'params_in', 'state', 'rot', 'params', 'labels', 'bbox', 'vertices', 'label',
+                                          'fwd', 'inv')]
+
+
 class MergeXform(C.Structure):
     _fields_ = [('scale', C.c_double), ('off_x', C.c_double), ('off_y', C.c_double)]
 
@@ -223,6 +240,10 @@ SIGNATURES = {
     'dbx_patch_augment': (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP]),
     'dbx_patch_aug_params_host': (C.c_int, [C.POINTER(PatchAugCfg), _I64, _I64, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP]),
     'dbx_patch_augment_host': (C.c_int, [_VP, _VP, _VP, _I32, _I32, _VP]),
+    'dbx_patch_warp_plan': (C.c_int, [C.POINTER(PatchWarpIO), C.POINTER(PatchWarpCfg), _I32, _VP]),
+    'dbx_patch_warp': (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _VP]),
+    'dbx_patch_warp_params_host': (C.c_int, [C.POINTER(PatchWarpCfg), _I64, _I64, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    'dbx_patch_warp_host': (C.c_int, [_VP, _VP, _VP, _I32, _VP]),
     'dbx_conv_wgrad_scratch_bytes': (_I64, [_I32, _PV, _PV, _I32, _I32]),
     'dbx_conv_wgrad': (C.c_int, [_I32, _PV, _PV, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _I32, _VP]),
     'dbx_conv_wgrad_slice': (C.c_int, [_I32, _PV, _PV, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP]),

@@ -3,6 +3,7 @@
 // file: `areas[i] + areas[j] - w*h` must round the product before the subtraction like NumPy does.
 #pragma clang fp contract(off)
 #include "common.hpp"
+#include "warp_px.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -1205,58 +1206,7 @@ extern "C" int dbx_merge_nms_thresh_batch(const double* const* level_dets, const
 // PUBLISHED algorithm (imgwarp.cpp): 8x8 system in double solved by LU with partial pivoting; inverse map through the
 // 3x3 inverse; source coordinates rounded to 1/32 pixel (INTER_BITS = 5); 8-bit bilinear weights in 15-bit fixed point,
 // (sum + 2^14) >> 15.  Parity with OpenCV itself is unpinned; the GPU kernel is bit-exact against oracle/.
-// The 8x8 solve of cv2.getPerspectiveTransform on double corner values: false where a pivot fails the test.  One function for the host
-// entry point and the crop kernel, so both do the same operations in the same order.  Every index is a loop counter (the pivot row is
-// found by comparing the counter with piv), so the device copy keeps A in registers once the loops are unrolled.
-__host__ __device__ static inline bool perspective_solve(const double* s, const double* d, double* m9) {
-    double A[8][9];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const double sx = s[2 * i], sy = s[2 * i + 1], dx = d[2 * i], dy = d[2 * i + 1];
-        const double r0[9] = {sx, sy, 1, 0, 0, 0, -sx * dx, -sy * dx, dx};
-        const double r1[9] = {0, 0, 0, sx, sy, 1, -sx * dy, -sy * dy, dy};
-#pragma unroll
-        for (int j = 0; j < 9; ++j) { A[i][j] = r0[j]; A[i + 4][j] = r1[j]; }
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {                      // Gaussian elimination, partial pivoting (DECOMP_LU)
-        int piv = c;
-        double best = fabs(A[c][c]);
-#pragma unroll
-        for (int r = c + 1; r < 8; ++r) {
-            const double v = fabs(A[r][c]);
-            if (v > best) { best = v; piv = r; }
-        }
-        if (!(best > 2.220446049250313e-16)) return false;
-#pragma unroll
-        for (int r = c + 1; r < 8; ++r) {
-            if (r == piv) {
-#pragma unroll
-                for (int j = 0; j < 9; ++j) { const double t = A[c][j]; A[c][j] = A[r][j]; A[r][j] = t; }
-            }
-        }
-        const double dd = -1.0 / A[c][c];
-#pragma unroll
-        for (int r = c + 1; r < 8; ++r) {
-            const double f = A[r][c] * dd;
-#pragma unroll
-            for (int j = c + 1; j < 9; ++j) A[r][j] += f * A[c][j];
-        }
-    }
-    double x[8];
-#pragma unroll
-    for (int r = 7; r >= 0; --r) {
-        double acc = A[r][8];
-#pragma unroll
-        for (int j = r + 1; j < 8; ++j) acc -= A[r][j] * x[j];
-        x[r] = acc / A[r][r];
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) m9[i] = x[i];
-    m9[8] = 1.0;
-    return true;
-}
-
+// perspective_solve, warp_px_u8 and warp_inverse live in warp_px.hpp: the patch warp (warp_aug_ops.hip) runs the same functions.
 extern "C" int dbx_perspective_matrix(const float* src_xy, const float* dst_xy, double* m9) {
     DBX_REQUIRE(src_xy && dst_xy && m9, "perspective_matrix: null argument");
     double s[8], d[8];
@@ -1265,48 +1215,12 @@ extern "C" int dbx_perspective_matrix(const float* src_xy, const float* dst_xy, 
     return DBX_OK;
 }
 
-// One output pixel of the warp at canvas coordinate (x, y): the inverse map in fp64, the source coordinate rounded to 1/32 pixel,
-// 15-bit bilinear weights, a zero border; channel ch of the result in byte ch.  Both warp kernels call it, so the batched one writes
-// what the single-image one writes, bit for bit (fp contraction is off for the whole file).
-template <typename SrcPtr>
-__device__ __forceinline__ unsigned int warp_px_u8(const double* im, SrcPtr src, int sh, int sw, int c, int x, int y) {
-    const double X0 = im[0] * x + im[1] * y + im[2], Y0 = im[3] * x + im[4] * y + im[5];
-    double W = im[6] * x + im[7] * y + im[8];
-    W = W != 0.0 ? 32.0 / W : 0.0;
-    const double fX = fmax(-2147483648.0, fmin(2147483647.0, X0 * W)), fY = fmax(-2147483648.0, fmin(2147483647.0, Y0 * W));
-    const int X = (int)rint(fX), Y = (int)rint(fY);                          // cvRound: nearest, ties to even
-    const int sx = X >> 5, sy = Y >> 5, ax = X & 31, ay = Y & 31;
-    const int w00 = (32 - ax) * (32 - ay) * 32, w01 = ax * (32 - ay) * 32, w10 = (32 - ax) * ay * 32, w11 = ax * ay * 32;
-    const bool x0 = sx >= 0 && sx < sw, x1 = sx + 1 >= 0 && sx + 1 < sw, y0 = sy >= 0 && sy < sh, y1 = sy + 1 >= 0 && sy + 1 < sh;
-    unsigned int px = 0;
-    for (int ch = 0; ch < c; ++ch) {
-        const int p00 = (x0 && y0) ? src[((size_t)sy * sw + sx) * c + ch] : 0;
-        const int p01 = (x1 && y0) ? src[((size_t)sy * sw + sx + 1) * c + ch] : 0;
-        const int p10 = (x0 && y1) ? src[((size_t)(sy + 1) * sw + sx) * c + ch] : 0;
-        const int p11 = (x1 && y1) ? src[((size_t)(sy + 1) * sw + sx + 1) * c + ch] : 0;
-        const int v = (p00 * w00 + p01 * w01 + p10 * w10 + p11 * w11 + (1 << 14)) >> 15;
-        px |= (unsigned int)(v < 0 ? 0 : (v > 255 ? 255 : v)) << (8 * ch);
-    }
-    return px;
-}
-
 struct WarpArgs { const unsigned char* src; unsigned char* dst; int sh, sw, c, dh, dw; double im[9]; };
 __global__ void warp_perspective_u8_kernel(const WarpArgs a) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= a.dw || y >= a.dh) return;
     const unsigned int px = warp_px_u8(a.im, a.src, a.sh, a.sw, a.c, x, y);
     for (int ch = 0; ch < a.c; ++ch) a.dst[((size_t)y * a.dw + x) * a.c + ch] = (unsigned char)(px >> (8 * ch));
-}
-
-// dst -> src map: the inverse of the 3x3 src -> dst map m, cofactor form in double.  False when the determinant is zero.
-__host__ __device__ static inline bool warp_inverse(const double* m, double* im) {
-    const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-    if (det == 0.0) return false;
-    const double d = 1.0 / det;
-    im[0] = (m[4] * m[8] - m[5] * m[7]) * d; im[1] = (m[2] * m[7] - m[1] * m[8]) * d; im[2] = (m[1] * m[5] - m[2] * m[4]) * d;
-    im[3] = (m[5] * m[6] - m[3] * m[8]) * d; im[4] = (m[0] * m[8] - m[2] * m[6]) * d; im[5] = (m[2] * m[3] - m[0] * m[5]) * d;
-    im[6] = (m[3] * m[7] - m[4] * m[6]) * d; im[7] = (m[1] * m[6] - m[0] * m[7]) * d; im[8] = (m[0] * m[4] - m[1] * m[3]) * d;
-    return true;
 }
 
 extern "C" int dbx_warp_perspective_u8(const uint8_t* src, int32_t sh, int32_t sw, int32_t c, const double* m9, uint8_t* dst,

@@ -322,15 +322,163 @@ def augment_patches(patches, plan_or_labels, augment=None, params=None, counter=
     return out, plan.labels_i32, plan.bbox, plan.vertices, plan.labels, plan.params
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# Geometric augmentation of the cut patches on the device (dbx_patch_warp_plan + dbx_patch_warp; include/densebox_hip.h, "training
+# patch warp"): rotation, scale, aspect, shear, translation and keystone as one perspective map per patch, with the labels carried
+# through it.  The reference has no augmentation: the semantics are this project's own, restated in tests/warp_aug_ref.py.
+WARP_FIELDS = ('flags', 'border', 'fill', 'rot', 'quad0', 'quad1', 'quad2', 'quad3', 'quad4', 'quad5', 'quad6', 'quad7', 'scale', 'aspect',
+               'shear', 'reserved')
+WARP_IDENTITY_QUAD = (0, 0, 3824, 0, 3824, 3824, 0, 3824)
+WARP_BORDERS = {'constant': 0, 'replicate': 1}
+
+
+def _q4(v):
+    return int(round(float(v) * 16.0))
+
+
+class Warp(object):
+    """A plain config of the geometric augmentation, from which cfg() makes the dbx_patch_warp_cfg struct and bank() the int32 [R, 2]
+    table of (cos, sin) * 65536, one row per whole degree of `rotate`.  p: the probability that a slot is warped; rotate: (lo, hi) whole
+    degrees, positive turning x towards y (clockwise on the screen); scale, aspect: (lo, hi) factors, held in Q8 (aspect multiplies the
+    width alone); shear: (lo, hi) of the x-by-y shear, Q8; translate, jitter: pixels, held in 1/16 pixel -- every corner of the quad moves
+    by the same translation and by a jitter of its own, which is what makes a keystone; margin: a positive whose warped vertices do not
+    all lie in margin .. 239 - margin keeps its un-warped patch and labels (8 is the reference's landmark rule); border: 'replicate' or
+    'constant' with fill, one byte per channel.  The defaults are a convention, not tuned: there are no trained weights in this tree to
+    tune them against."""
+
+    def __init__(self, p=0.8, rotate=(-15, 15), scale=(0.85, 1.15), aspect=(0.9, 1.1), shear=(-0.1, 0.1), translate=8, jitter=6, margin=8,
+                 border='replicate', fill=(0, 0, 0, 0), seed=0):
+        if border not in WARP_BORDERS:
+            raise RuntimeError("Warp: border=%r must be 'constant' or 'replicate'" % (border,))
+        fill = tuple(int(v) for v in (fill if np.ndim(fill) else (fill,) * 4))
+        if len(fill) > 4 or any(v < 0 or v > 255 for v in fill):
+            raise RuntimeError('Warp: fill=%r must be at most 4 bytes' % (fill,))
+        if int(rotate[0]) != rotate[0] or int(rotate[1]) != rotate[1] or rotate[0] > rotate[1]:
+            raise RuntimeError('Warp: rotate=%r must be whole degrees, lo <= hi' % (rotate,))
+        self.p, self.seed, self.margin, self.border = float(p), int(seed), int(margin), border
+        self.rotate, self.scale, self.aspect, self.shear = (int(rotate[0]), int(rotate[1])), tuple(scale), tuple(aspect), tuple(shear)
+        self.translate, self.jitter, self.fill = float(translate), float(jitter), fill + (0,) * (4 - len(fill))
+        self._bank = None
+
+    @classmethod
+    def identity(cls, seed=0):
+        """The no-op: no slot is warped, every record carries the identity quad, and the kernel copies."""
+        return cls(p=0.0, rotate=(0, 0), scale=(1.0, 1.0), aspect=(1.0, 1.0), shear=(0.0, 0.0), translate=0, jitter=0, seed=seed)
+
+    def cfg(self):
+        f = _lib.PatchWarpCfg()
+        f.p_warp = self.p
+        f.R = self.rotate[1] - self.rotate[0] + 1
+        f.rot_lo, f.rot_hi = 0, f.R - 1
+        f.scale_lo, f.scale_hi = _q8(self.scale[0]), _q8(self.scale[1])
+        f.aspect_lo, f.aspect_hi = _q8(self.aspect[0]), _q8(self.aspect[1])
+        f.shear_lo, f.shear_hi = _q8(self.shear[0]), _q8(self.shear[1])
+        f.tx = f.ty = _q4(self.translate)
+        f.jitter, f.margin, f.border = _q4(self.jitter), self.margin, WARP_BORDERS[self.border]
+        f.fill = int(np.array(self.fill, dtype=np.uint8).view('<i4')[0])
+        return f
+
+    def bank(self):
+        """int32 [R, 2]: (rint(cos * 65536), rint(sin * 65536)) of rotate[0] .. rotate[1] degrees, made once on the host."""
+        if self._bank is None:
+            t = np.deg2rad(np.arange(self.rotate[0], self.rotate[1] + 1, dtype=np.float64))
+            self._bank = np.stack([np.rint(np.cos(t) * 65536.0), np.rint(np.sin(t) * 65536.0)], axis=1).astype(np.int32)
+        return self._bank
+
+
+class WarpPlan(object):
+    """The device tensors one dbx_patch_warp_plan launch writes: params int32 [n, 16] (dbx_patch_warp_rec records, WARP_FIELDS), labels_i32
+    int32 [n, 12], bbox float32 [n, 4], vertices [n, 8], labels [n, 1], fwd / inv float64 [n, 9] (input -> output and output -> input;
+    the exact identity for a slot that copies).  Rows at or past the count are not written (the tensors start zeroed)."""
+
+    def __init__(self, n, device):
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+        self.n = int(n)
+        self.params, self.labels_i32 = z((n, 16), torch.int32), z((n, 12), torch.int32)
+        self.bbox, self.vertices, self.labels = z((n, 4), torch.float32), z((n, 8), torch.float32), z((n, 1), torch.float32)
+        self.fwd, self.inv = z((n, 9), torch.float64), z((n, 9), torch.float64)
+
+
+def plan_warp(labels_i32, count, cfg, bank=None, params=None, state=None, out=None):
+    """The dbx_patch_warp_plan launch alone, on the current stream.  labels_i32 int32 [n, 12] and count int32 [1]: device tensors (a
+    PatchPlan's); cfg: Warp.cfg(); bank: device int32 [R, 2] (Warp.bank(), uploaded); params int32 [n, 16] (injected mode) or state int64
+    [2] = (seed, counter) (device mode), device tensors.  Returns the WarpPlan (`out`, or a new one)."""
+    n = int(labels_i32.size(0))
+    out = out if out is not None else WarpPlan(n, labels_i32.device)
+    io = _lib.PatchWarpIO()
+    io.labels_in, io.count = labels_i32.data_ptr(), count.data_ptr()
+    io.params_in = params.data_ptr() if params is not None else None
+    io.state = state.data_ptr() if state is not None else None
+    io.rot = bank.data_ptr() if bank is not None and bank.numel() else None
+    io.params, io.labels, io.bbox, io.vertices, io.label = out.params.data_ptr(), out.labels_i32.data_ptr(), out.bbox.data_ptr(), \
+        out.vertices.data_ptr(), out.labels.data_ptr()
+    io.fwd, io.inv = out.fwd.data_ptr(), out.inv.data_ptr()
+    _lib.check(_lib.lib().dbx_patch_warp_plan(C.byref(io), C.byref(cfg), n, _lib.stream_ptr()))
+    return out
+
+
+def apply_warp(patches, params, inv, count, out=None):
+    """The dbx_patch_warp launch alone: patches uint8 [n, 240, 240, c] (any byte alignment) through the records params int32 [n, 16] and
+    the matrices inv float64 [n, 9] into `out` (a new zeroed tensor when None; it may not overlap patches).  Slots at or past the count
+    keep what they held."""
+    if patches.dtype != torch.uint8 or patches.dim() != 4 or tuple(patches.shape[1:3]) != (PATCH_SIDE, PATCH_SIDE) or not patches.is_contiguous():
+        raise RuntimeError('apply_warp: patches must be a contiguous uint8 [n, 240, 240, c] tensor, got %s %s' % (patches.dtype, list(patches.shape)))
+    if out is None:
+        out = torch.zeros_like(patches)
+    if out.dtype != torch.uint8 or out.shape != patches.shape or not out.is_contiguous():
+        raise RuntimeError('apply_warp: out must be a contiguous uint8 %s tensor, got %s %s' % (list(patches.shape), out.dtype, list(out.shape)))
+    n = int(patches.size(0))
+    if params.dtype != torch.int32 or params.numel() != 16 * n or inv.dtype != torch.float64 or inv.numel() != 9 * n \
+            or not params.is_contiguous() or not inv.is_contiguous():
+        raise RuntimeError('apply_warp: params must be int32 [%d, 16] and inv float64 [%d, 9], got %s %s and %s %s'
+                           % (n, n, params.dtype, list(params.shape), inv.dtype, list(inv.shape)))
+    _lib.check(_lib.lib().dbx_patch_warp(C.c_void_p(patches.data_ptr()), C.c_void_p(params.data_ptr()), C.c_void_p(inv.data_ptr()),
+                                         C.c_void_p(count.data_ptr()), n, int(patches.size(3)), C.c_void_p(out.data_ptr()),
+                                         _lib.stream_ptr()))
+    return out
+
+
+def warp_patches(patches, plan_or_labels, warp=None, params=None, counter=0):
+    """One upload + the two launches, for patches a user already has.  patches: uint8 [n, 240, 240, c], host or device; plan_or_labels: a
+    PatchPlan (its label rows and count) or the int [n, 12] label rows (then all n slots count); warp: a Warp (None: the default one);
+    params: int [n, 16] records (injected mode), else they are drawn from (warp.seed, counter).  Returns (out, labels_i32, bbox, vertices,
+    labels, params, fwd, inv): the warped patches, the four label tensors, the records used and the two matrices of every slot."""
+    warp = warp if warp is not None else Warp()
+    dev = patches if torch.is_tensor(patches) else torch.from_numpy(np.ascontiguousarray(patches))
+    dev = dev.cuda()
+    n = int(dev.size(0))
+    parts = [warp.bank().reshape(-1), np.array([warp.seed, counter], dtype=np.int64)]
+    if params is not None:
+        rec = params.cpu().numpy() if torch.is_tensor(params) else np.asarray(params)
+        parts.append(np.ascontiguousarray(rec.astype(np.int32).reshape(n, 16)))
+    if isinstance(plan_or_labels, PatchPlan):
+        labels_in, count = plan_or_labels.labels_i32, plan_or_labels.count
+    else:
+        rows = plan_or_labels.cpu().numpy() if torch.is_tensor(plan_or_labels) else np.asarray(plan_or_labels)
+        parts += [np.ascontiguousarray(rows.astype(np.int32).reshape(n, 12)), np.array([n], dtype=np.int32)]
+        labels_in = count = None
+    up = _upload(*parts)
+    if labels_in is None:
+        labels_in, count = up[-2], up[-1]
+    plan = plan_warp(labels_in, count, warp.cfg(), bank=up[0].view(-1, 2), params=up[2] if params is not None else None, state=up[1])
+    out = apply_warp(dev, plan.params, plan.inv, count)
+    return out, plan.labels_i32, plan.bbox, plan.vertices, plan.labels, plan.params, plan.fwd, plan.inv
+
+
 class PatchSampler(object):
     """Fresh training patches every step with frames, tables, state and outputs resident on the device.  frames / plates: as for
     sample_patches; n: patches per batch; every batch decides ceil(oversample * n) candidates (at most 4096), of which a fraction
     neg_frac are pure negatives.  next_batch() is the two launches plus a 4-byte read of the count.  augment: an Augment; then
     launch() adds dbx_patch_aug_plan + dbx_patch_augment after the cut, into a second buffer of the sampler's, and next_batch() returns
     the augmented patches and labels; `raw` and `plan` still hold the un-augmented ones, `aug_params` the records used (int32 [n, 16]).
-    The augmenter's state (augment.seed, counter) is its own: the plan's draws do not depend on it."""
+    The augmenter's state (augment.seed, counter) is its own: the plan's draws do not depend on it.  warp: a Warp; then launch() adds
+    dbx_patch_warp_plan + dbx_patch_warp between the cut and the augmenter (cut -> warp -> augment: the augmenter reads the warp's label
+    rows and pixels), into a buffer of the sampler's; `warped` holds the warped patches before any photometry, `warp_plan` their labels
+    and matrices, `warp_params` the records used.  next_batch() returns the last stage's tensors.  The warper's state (warp.seed,
+    counter) is its own as well."""
 
-    def __init__(self, frames, plates, n, oversample=1.5, neg_frac=0.1, seed=0, offset_radius=15, th=0, allow_short=False, augment=None):
+    def __init__(self, frames, plates, n, oversample=1.5, neg_frac=0.1, seed=0, offset_radius=15, th=0, allow_short=False, augment=None,
+                 warp=None):
         if int(n) < 1 or not oversample >= 1.0:
             raise RuntimeError('PatchSampler: n=%r must be positive and oversample=%r at least 1' % (n, oversample))
         host, _ = host_images('PatchSampler', frames, None)
@@ -344,6 +492,15 @@ class PatchSampler(object):
         self.plan = PatchPlan(self.M, self.n, self.table.device)
         self.patches = torch.zeros((self.n, PATCH_SIDE, PATCH_SIDE, self.c), dtype=torch.uint8, device=self.table.device)
         self.totals = torch.zeros(8, dtype=torch.int64, device=self.table.device)
+        self.warp = warp
+        if warp is not None:
+            self.rot_bank, self.warp_state = _upload(warp.bank().reshape(-1), np.array([warp.seed, 0], dtype=np.int64))
+            self.rot_bank = self.rot_bank.view(-1, 2)
+            self.warp_cfg = warp.cfg()
+            self.warp_plan = WarpPlan(self.n, self.table.device)
+            self.warped = torch.zeros_like(self.patches)
+        else:
+            self.warp_plan = self.warped = None
         self.augment = augment
         if augment is not None:
             bank = augment.curves()
@@ -363,15 +520,24 @@ class PatchSampler(object):
     def aug_params(self):
         return self.aug.params if self.augment is not None else None
 
+    @property
+    def warp_params(self):
+        return self.warp_plan.params if self.warp is not None else None
+
     def launch(self):
         """The launches (and the tally's accumulation) on the current stream, without any read: what a graph capture holds."""
         plan_patches(self.table, len(self.frames), self.c, self.plates, self.plate0, self.M, self.n, state=self.state,
                      neg_frac=self.neg_frac, offset_radius=self.offset_radius, th=self.th, out=self.plan)
         cut_patches(self.plan, self.c, self.patches)
         self.totals += self.plan.tally
+        labels_i32, pixels = self.plan.labels_i32, self.patches
+        if self.warp is not None:
+            plan_warp(labels_i32, self.plan.count, self.warp_cfg, bank=self.rot_bank, state=self.warp_state, out=self.warp_plan)
+            apply_warp(pixels, self.warp_plan.params, self.warp_plan.inv, self.plan.count, self.warped)
+            labels_i32, pixels = self.warp_plan.labels_i32, self.warped
         if self.augment is not None:
-            plan_augment(self.plan.labels_i32, self.plan.count, self.aug_cfg, state=self.aug_state, out=self.aug)
-            apply_augment(self.patches, self.aug.params, self.plan.count, self.curves, self.aug_patches)
+            plan_augment(labels_i32, self.plan.count, self.aug_cfg, state=self.aug_state, out=self.aug)
+            apply_augment(pixels, self.aug.params, self.plan.count, self.curves, self.aug_patches)
 
     def next_batch(self, allow_short=None):
         """(patches uint8 [n, 240, 240, C], bbox [n, 4], vertices [n, 8], labels [n, 1], count): net.forward's and net.loss's inputs.
@@ -384,6 +550,8 @@ class PatchSampler(object):
                                % (count, self.M, self.n, self.plan.tally.tolist()))
         if self.augment is not None:
             return self.aug_patches, self.aug.bbox, self.aug.vertices, self.aug.labels, count
+        if self.warp is not None:
+            return self.warped, self.warp_plan.bbox, self.warp_plan.vertices, self.warp_plan.labels, count
         return self.patches, self.plan.bbox, self.plan.vertices, self.plan.labels, count
 
     def status_tally(self):

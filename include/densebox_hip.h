@@ -72,7 +72,9 @@ const char* dbx_last_error(void);
  *      also at 13, without a bump: dbx_head2_up_plan_t, dbx_head2_backward_up_plan (which launches dbx_head2_backward_up makes: a
  *      read-only host query), a pure addition likewise
  *      also at 13, without a bump: dbx_upsample_bwd_plan_t, dbx_upsample_bilinear_bwd_plan (which kernel dbx_upsample_bilinear_bwd
- *      launches: a read-only host query), a pure addition likewise */
+ *      launches: a read-only host query), a pure addition likewise
+ *      also at 13, without a bump: dbx_patch_warp_rec, dbx_patch_warp_cfg, dbx_patch_warp_io, dbx_patch_warp_plan, dbx_patch_warp,
+ *      dbx_patch_warp_params_host, dbx_patch_warp_host (training patches warped on the device), pure additions likewise */
 #define DBX_ABI_VERSION 13
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
@@ -1152,6 +1154,105 @@ int dbx_patch_aug_params_host(const dbx_patch_aug_cfg* cfg, int64_t seed, int64_
                               float* vertices, float* label);
 /* dbx_patch_augment of ONE patch [240][240][c] on the host.  Refusals as for dbx_patch_augment. */
 int dbx_patch_augment_host(const uint8_t* patch, const dbx_patch_aug* rec, const uint8_t* curves, int32_t G, int32_t c, uint8_t* out);
+
+/* ---- training patch warp (this project's own semantics: the reference has no augmentation; tests/warp_aug_ref.py restates them) ----
+ * The geometric half of the augmenter: rotation, scale, aspect, shear, translation and keystone of a cut patch, as ONE perspective
+ * map per slot.  Two launches between dbx_patch_cut and dbx_patch_aug_plan and no host read: dbx_patch_warp_plan (ONE workgroup) decides
+ * a record, the label row and the two 3 x 3 matrices of every slot; dbx_patch_warp (n * 15 workgroups, fixed by n alone) makes the
+ * pixels, out of place.  fp contraction is off in the whole file, as for the rectification: host and device round alike.
+ *
+ * Quad and matrices.  A warp is given by a quad: eight int32 in 1/16 pixel, the places in the OUTPUT patch where the input patch's
+ * corner pixel centres (0,0), (239,0), (239,239), (0,239) land, in that order; the identity quad is (0,0, 3824,0, 3824,3824, 0,3824).
+ * fwd = M = the 8 x 8 solve of dbx_perspective_matrix on (square, quad / 16.0) in double (the division is exact); inv = the cofactor
+ * inverse dbx_warp_perspective_u8 takes of M.
+ *
+ * Pixels.  Output pixel (x, y) of a warped slot is dbx_warp_perspective_u8's arithmetic on the 240 x 240 input patch with inv: the
+ * float64 inverse map, cvRound to 1/32 pixel, 15-bit bilinear weights, (sum + 2^14) >> 15.  border 0 (constant): a neighbour outside the
+ * patch contributes byte ch of fill (one byte per channel, channel ch in bits 8 ch .. 8 ch + 7); with fill 0 this is exactly
+ * dbx_warp_perspective_u8.  border 1 (replicate): the four neighbour coordinates are clamped to 0..239.  A slot whose warp is not
+ * applied (bit 0 of the written record clear) is a copy of its input.
+ *
+ * Labels.  labels_in int32 [n][12] as dbx_patch_plan writes them (box, lu, ru, rd, ld); twelve zeros are a negative, which keeps its
+ * zero row and has its pixels warped.  A positive: each vertex (vx, vy) goes through M in float64, left to right:
+ *   W = m6 * vx + m7 * vy + m8;  x' = I((m0 * vx + m1 * vy + m2) / W);  y' = I((m3 * vx + m4 * vy + m5) / W);  I(v) = v + 0.5 truncated
+ *   toward zero;  the box is rebuilt as the plan builds it: bx0 = min(lu.x, ld.x), bx1 = max(ru.x, rd.x), by0 = min(lu.y, ru.y),
+ *   by1 = max(ld.y, rd.y).  bbox = labels[0..3] / 4, vertices = labels[4..11] / 4, label = 1 (0 for a negative) as float32.
+ * Refused by rule (a positive only): any W not finite or not > 0; any new vertex coordinate outside margin .. 239 - margin (a value
+ * that is not finite counts as outside); bx1 <= bx0 or by1 <= by0.  A refused positive copies its pixels and its label row; bit 0 is
+ * cleared and bit 1 set.
+ * Degenerate (any slot that asks for the warp): the solve or the inverse fails (a pivot at or below 2^-52, a zero determinant), or any
+ * of the 18 matrix entries is not finite.  A degenerate slot copies; bit 0 is cleared and bit 2 set.  Degeneracy is decided before the
+ * label rule.  fwd and inv of every slot that copies are the exact identity.
+ *
+ * dbx_patch_warp_rec (64 bytes, 16 int32): flags 0 (bit 0: warp applied, bit 1: refused by the label rule, bit 2: degenerate), border 4
+ * (0 constant, 1 replicate), fill 8, rot 12 (a row of the bank), quad 16 (8 x int32), scale 48 (Q8), aspect 52 (Q8), shear 56 (Q8, signed),
+ * reserved 60 (0).  What a kernel reads of a record ("sanitised", the same function on host and device): flags & 1; a border outside
+ * 0..1 is 0; quad entries are clamped to +-2^20; reserved is 0.  rot, scale, aspect and shear are carried, never read back.  The records
+ * written out are the sanitised ones with the refusal bits.
+ *
+ * Parameters.
+ *   injected mode (io->params_in non-NULL): slot s reads params_in[s]; bit 0 of flags asks for the warp, bits 1 and 2 are ignored.
+ *   device mode (params_in NULL): from h(seed, counter, s, j) of the sampler's hash with a FIXED draw number j per field, whether or not
+ *   the warp is on; k = h >> 11; a range is lo + k mod (hi - lo + 1):
+ *     j = 0 warp on: k * 2^-53 < p_warp;  1 rot in rot_lo..rot_hi;  2 scale;  3 aspect;  4 shear;  5 tx in -tx..tx;  6 ty in -ty..ty;
+ *     7 + i the jitter of quad[i] in -jitter..jitter (i = 0..7: jx_0, jy_0, jx_1, ...).  border and fill are the cfg's.
+ *   No trigonometry on the device: rot is a row of a host-built bank, device int32 [R][2] = (rint(cos * 65536), rint(sin * 65536)).
+ *   The quad, in int64 with arithmetic shifts, for corner k with (px, py) = (-1912,-1912), (1912,-1912), (1912,1912), (-1912,1912)
+ *   (119.5 pixels = 1912 / 16):
+ *     u = (px * scale * aspect) >> 16;  v = (py * scale) >> 8;  u += (shear * v) >> 8;
+ *     x = (cos * u - sin * v + 32768) >> 16;  y = (sin * u + cos * v + 32768) >> 16;
+ *     quad[2k] = x + 1912 + tx + jx_k;  quad[2k + 1] = y + 1912 + ty + jy_k, each clamped to +-2^20 as the sanitiser would.
+ *   A slot whose warp is off gets the identity quad (and does not read the bank); its other drawn fields are written as drawn.
+ *   state = device int64 [2] = (seed, counter), the warper's own; the launch's last act is counter += 1.  The plan's and the
+ *   augmenter's draws do not depend on it.
+ * dbx_patch_warp_cfg (72 bytes): p_warp 0 (double); rot_lo 8, rot_hi 12; scale_lo 16, scale_hi 20; aspect_lo 24, aspect_hi 28; shear_lo
+ * 32, shear_hi 36; tx 40, ty 44, jitter 48 (1/16 pixel, magnitudes); margin 52 (pixels; 8 is the reference's landmark rule); border 56;
+ * fill 60; R 64 (rows of the bank); reserved 68 (0). */
+typedef struct dbx_patch_warp_rec {
+    int32_t flags, border, fill, rot;
+    int32_t quad[8];
+    int32_t scale, aspect, shear, reserved;
+} dbx_patch_warp_rec;
+typedef struct dbx_patch_warp_cfg {
+    double p_warp;
+    int32_t rot_lo, rot_hi, scale_lo, scale_hi, aspect_lo, aspect_hi, shear_lo, shear_hi;
+    int32_t tx, ty, jitter, margin, border, fill, R;
+    int32_t reserved;
+} dbx_patch_warp_cfg;
+/* device pointers of dbx_patch_warp_plan (96 bytes: 12 pointers in this order) */
+typedef struct dbx_patch_warp_io {
+    const int32_t* labels_in;             /* [n][12] */
+    const int32_t* count;                 /* [1] */
+    const dbx_patch_warp_rec* params_in;  /* [n], or NULL: device mode */
+    int64_t* state;                       /* [2] (seed, counter); needed in device mode only */
+    const int32_t* rot;                   /* [R][2] (cos, sin) * 65536; needed in device mode with p_warp > 0 only */
+    dbx_patch_warp_rec* params;           /* [n] */
+    int32_t* labels;                      /* [n][12] */
+    float* bbox;                          /* [n][4] */
+    float* vertices;                      /* [n][8] */
+    float* label;                         /* [n][1] */
+    double* fwd;                          /* [n][9] */
+    double* inv;                          /* [n][9] */
+} dbx_patch_warp_io;
+/* cfg is a HOST struct, needed in both modes (injected mode reads margin alone).  Rows at or past min(count, n) are not written.
+ * Refused with DBX_ERR_ARG before anything is queued: a null io, cfg or pointer (params_in may be NULL: device mode, which needs state,
+ * and with p_warp > 0 the bank), n outside 1..4096, and a cfg with: p_warp outside [0, 1]; a range with lo > hi; scale or aspect outside
+ * 1..65535; |shear| above 65535; tx, ty or jitter outside 0..2^16; margin outside 0..119; border outside 0..1; R outside 0..65536; |rot|
+ * above 2^20; with p_warp > 0 a rot range that leaves the bank (0 <= rot_lo <= rot_hi < R). */
+int dbx_patch_warp_plan(const dbx_patch_warp_io* io, const dbx_patch_warp_cfg* cfg, int32_t n, void* stream);
+/* patches, out: device uint8 [n][240][240][c] at any byte address; params / inv / count as dbx_patch_warp_plan left them (or any: the
+ * records are sanitised, and whatever inv holds no read leaves the slot's patch).  Slot s < min(count, n) is written, every other byte of
+ * out is left alone; a slot with bit 0 clear is copied.  Out of place only.  Refused: a null pointer, c outside 1..4, n outside 1..4096,
+ * patches and out overlapping. */
+int dbx_patch_warp(const uint8_t* patches, const dbx_patch_warp_rec* params, const double* inv, const int32_t* count, int32_t n, int32_t c,
+                   uint8_t* out, void* stream);
+/* dbx_patch_warp_plan on the host (the same __host__ __device__ functions) for slots 0 .. count - 1, count in 0..4096: params_in NULL
+ * derives from (seed, counter) and rot (a HOST bank).  Refusals as for dbx_patch_warp_plan. */
+int dbx_patch_warp_params_host(const dbx_patch_warp_cfg* cfg, int64_t seed, int64_t counter, const dbx_patch_warp_rec* params_in,
+                               const int32_t* rot, const int32_t* labels_in, int32_t count, dbx_patch_warp_rec* params, int32_t* labels,
+                               float* bbox, float* vertices, float* label, double* fwd, double* inv);
+/* dbx_patch_warp of ONE patch [240][240][c] on the host with its record and its inv [9].  Refusals as for dbx_patch_warp. */
+int dbx_patch_warp_host(const uint8_t* patch, const dbx_patch_warp_rec* rec, const double* inv, int32_t c, uint8_t* out);
 
 /* ---- data-parallel gradient exchange (new capability; the reference is single-GPU) ----
  * One process per GPU.  Rank 0 makes a 128-byte id (dbx_dp_unique_id) and hands it to the other ranks by any host channel;
