@@ -153,9 +153,12 @@ __device__ __forceinline__ u32x4 genhid_wfrag(const GenHid& gh, int hd, int ch, 
     }
     return raw;
 }
-// pixel of frame position q (inside one image's frame, row-major over wp columns): compact index m = (img * H + y) * W + x, or -1 in the halo
+// pixel of frame position q (inside one image's frame, row-major over wp columns): compact index m = (img * H + y) * W + x, or -1 in the halo.
+// NOT CALLED by any kernel at present: wgrad_wide2_kernel<T, true> divides once per workgroup and then walks incrementally, the data-gradient
+// generator walks compact pixels.  Kept for a consumer that needs a random-access lookup; its float row recovery is exact for q < 2**22 at
+// every wp in 32 .. 4100 and first wrong at q = 4 201 469, wp = 4095 (tests/test_heads1_ref.py sweeps a NumPy float32 emulation of this line)
 __device__ __forceinline__ int genhid_pixel(const GenHid& gh, int img, int q_in_img, int wp, float inv_wp) {
-    const int fy = (int)(((float)q_in_img + 0.5f) * inv_wp);         // exact: (q + 0.5) / wp is >= 0.5 / wp away from an integer
+    const int fy = (int)(((float)q_in_img + 0.5f) * inv_wp);         // inv_wp = 1.f / wp; see the domain above
     const int fx = q_in_img - fy * wp;
     const int y = fy - gh.pad, x = fx - gh.pad;
     return ((unsigned)y < (unsigned)gh.H && (unsigned)x < (unsigned)gh.W) ? (img * gh.H + y) * gh.W + x : -1;

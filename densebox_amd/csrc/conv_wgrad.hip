@@ -2296,6 +2296,9 @@ extern "C" int dbx_conv_wgrad_pool_dz(int32_t dtype, const dbx_view* dy, const v
 // Scratch: dbx_conv_wgrad_scratch_bytes for a dz view of 512 * nh channels congruent with x.
 int dbx_internal_heads1_wgrad_gen_f32(const dbx_view* d_out, const dbx_view* x, const float* const* w2, const int32_t* k, int nh, int use_hash,
                                       unsigned seed, int ci, float* dw, int ci_total, int ci_off, float* db, hipStream_t s);
+static bool heads1_gen_extent_ok(const dbx_view* x) {
+    return (int64_t)x->n * x->h * x->w < ((int64_t)1 << 24);           // gfetch: __umul24(compact pixel index, slot stride)
+}
 template <typename T>
 static int heads1_wgrad_gen_t(const dbx_view* d_out, const dbx_view* x, const float* const* w2, const int32_t* k, int nh, int use_hash, unsigned seed,
                               int ci, float* dw, int ci_total, int ci_off, float* db, void* scratch, hipStream_t s) {
@@ -2307,6 +2310,8 @@ static int heads1_wgrad_gen_t(const dbx_view* d_out, const dbx_view* x, const fl
         DBX_REQUIRE(d_out->c % nh == 0 && d_out->c / nh >= 8 && ((size_t)d_out->ptr % 16) == 0 && (d_out->ld * 2) % 16 == 0 && (d_out->c_off * 2) % 16 == 0 &&
                     ((d_out->c / nh) * 2) % 16 == 0, "heads1_wgrad_gen: d_out slots of >= 8 channels, 16-byte aligned");
         DBX_REQUIRE((int64_t)d_out->n * d_out->h * d_out->w * d_out->ld * 2 < ((int64_t)1 << 31), "heads1_wgrad_gen: d_out beyond 2 GiB");
+        // the generator multiplies a compact pixel index by the slot stride with a 24-bit multiply (as dbx_heads1_dgrad_gen requires too)
+        DBX_REQUIRE(heads1_gen_extent_ok(x), "heads1_wgrad_gen: needs fewer than 2**24 pixels");
         GenHid g;
         g.dout = (const char*)d_out->ptr + (size_t)d_out->c_off * 2;
         for (int i = 0; i < 4; ++i) {
@@ -2326,7 +2331,7 @@ extern "C" int dbx_heads1_wgrad_gen_ok(int32_t dtype, const dbx_view* x, int32_t
     dbx_view dz = *x;
     dz.c = dz.ld = 512 * nh; dz.c_off = 0;
     const WgradPlan p = wgrad_plan(dtype, &dz, x, 1, 1);
-    return (p.wide2 && p.spi > 0) ? 1 : 0;
+    return (p.wide2 && p.spi > 0 && heads1_gen_extent_ok(x)) ? 1 : 0;
 }
 extern "C" int dbx_heads1_wgrad_gen(int32_t dtype, const dbx_view* d_out, const dbx_view* x, const float* const* w2, const int32_t* k, int32_t nh,
                                     int32_t use_hash, uint32_t drop_seed, int32_t ci, float* dw_oihw, int32_t dw_ci_total, int32_t dw_ci_off,

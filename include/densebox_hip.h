@@ -265,7 +265,9 @@ int dbx_conv_wgrad_pool_dz(int32_t dtype, const dbx_view* dy, const void* idx, i
  * its consumers GENERATE it, 32 channels x 32 pixels per MFMA (W2 and d_out in the compute dtype, keep bits from the forward's hash):
  *   dbx_head2_backward_up with d_hid->ptr == NULL (the view's shape still describes the map) does not store it (one-pass form
  *     only: dbx_head2_backward_up_fused() == 1; hash dropout or none; it rounds W2 to the compute dtype like the generators),
- *   dbx_heads1_wgrad_gen = dbx_conv_wgrad_slice(d_hid, x, 1x1, ...) (x on a padded frame of >= 32 columns: dbx_heads1_wgrad_gen_ok()),
+ *   dbx_heads1_wgrad_gen = dbx_conv_wgrad_slice(d_hid, x, 1x1, ...) (x on a padded frame of >= 32 columns: dbx_heads1_wgrad_gen_ok();
+ *     16-bit types: fewer than 2**24 pixels N H W in all -- the generator's 24-bit index multiply, the bound dbx_heads1_dgrad_gen has
+ *     too; at or beyond it the call is refused and dbx_heads1_wgrad_gen_ok() is 0),
  *   dbx_heads1_dgrad_gen = dbx_conv_forward(d_hid, W1^T, DBX_EPI_GATE) -> y (256 channels; w1t_frag = dbx_pack_weight mode 5 image,
  *     rows_pad 256, cin_pad 512 nh).
  * d_out: the compact [N, H, W] map (pad 0) with one slot of >= 8 channels per head, channels >= k[i] zero; w2[i]: fp32 [k[i]][512].
