@@ -4,6 +4,8 @@ HIP kernels of libdensebox_hip.so for forward / backward of the three DenseBox n
 torch is used for device memory, streams and autograd bookkeeping only; every FLOP of the
 network runs in the library.  Layer graph = DenseBox.py:180-228 / :412-473 / :674-738.
 """
+import collections
+import contextlib
 import ctypes as C
 import os
 import weakref
@@ -38,6 +40,15 @@ _CH = {s: (ci, co) for s, ci, co in [('conv1_1_1', 3, 64), ('conv1_2_1', 64, 64)
                                      ('conv3_1_1', 128, 256), ('conv3_2_1', 256, 256), ('conv3_4_1', 256, 256),
                                      ('conv4_1_1', 256, 512), ('conv4_2_1', 512, 512), ('conv4_3_1', 512, 512),
                                      ('conv4_4_1', 512, 512)]}
+
+
+# One packed image of a plan's manifest (Engine._manifest): cache key, source parameter names, element type, pack mode (dbx_pack_weight's
+# 0 / 1 = forward / data-gradient order, 4 / 5 = the same in MFMA-fragment order for the register-streamed-weights kernel; 2 = fp32 bias
+# vector of rows_pad elements), geometry, and the (row_off, k_off) at which each source lands (negative: a channel slice, rows outside are skipped)
+Image = collections.namedtuple('Image', 'key srcs dt mode kh kw rows_pad cin_pad place')
+# dbx_pack_multi's 56-byte job record, field for field
+PackJob = collections.namedtuple('PackJob', 'src dst co ci taps mode ktot cin_pad row_off k_off rows_lim')
+_TNAME = ('f16', 'bf16', 'f32')
 
 
 def _align(x, a=256):
@@ -163,7 +174,7 @@ class Plan:
         if not train:
             self.heads_gen = False
         self.drop_active = self.drop_hash = False
-        self.frag = {}             # (stem, 'f' | 'b') -> fragment-order weights? (Engine._frag)
+        self.manifest = None       # role -> Image: every packed weight / bias this plan's step reads (Engine._manifest)
         self.drop_seed = 0
         self.mask_buf = None
         self.ws = torch.zeros(off, dtype=torch.uint8, device=device)
@@ -213,6 +224,25 @@ def engine_of(params):
     return eng
 
 
+class _Timed:
+    """Engine._timed with profiling on."""
+
+    def __init__(self, prof, name, flops):
+        self.prof, self.name, self.flops = prof, name, flops
+
+    def __enter__(self):
+        self.ev0, self.ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        self.ev0.record()
+
+    def __exit__(self, etype, exc, tb):
+        if etype is None:
+            self.ev1.record()
+            self.prof.append({'kernel': self.name() if callable(self.name) else self.name, 'flops': self.flops, 'start': self.ev0, 'end': self.ev1})
+
+
+_NOT_TIMED = contextlib.nullcontext()
+
+
 class Engine:
     def __init__(self, net):
         self.net = net
@@ -224,8 +254,6 @@ class Engine:
         self.last_plan = None
         self.grad_sink = None      # optional dist.GradReducer: flat gradient views + readiness callbacks
         self.profile = None        # list -> every conv / wgrad launch appends {kernel, flops, start, end} (HIP events)
-        self._defer = None         # not None while the multi-tensor pack table is being recorded
-        self._defer_keep = []
         self._table_keys = set()   # cache keys whose buffers the pack table refreshes
         self._tables = {}          # (dtype, train) -> (device job table, count, max_elems)
         self._wsig = None
@@ -253,61 +281,154 @@ class Engine:
         mod, attr = name.rsplit('.', 1)
         return getattr(getattr(self.net, mod), attr)
 
-    def _packed(self, key, builder, versions):
-        ent = self.wcache.get(key)
-        if ent is not None and (ent[0] == versions or key in self._table_keys):
-            return ent[1]       # table-covered buffers were refreshed by _prepare_weights() at the top of forward
-        # re-pack into the existing buffer when there is one: its zero padding never changes
-        t = builder(ent[1] if ent is not None else None)
-        self.wcache[key] = (versions, t)
-        return t
+    def _buffer(self, im, device):
+        """Zeroed storage of one image (its zero padding is never written again)."""
+        if im.mode == 2:
+            return torch.zeros(im.rows_pad, dtype=torch.float32, device=device)
+        d = ConvDesc(im.dt, im.kh, im.kw, 0, im.cin_pad, im.rows_pad, 0, 0)
+        return torch.zeros(self.L.dbx_conv_packed_elems(C.byref(d)) * _lib.ESIZE[im.dt], dtype=torch.uint8, device=device)
 
     def _pack(self, dt, mode, w, rows_pad, cin_pad, kh, kw, out=None, row_off=0, k_off=0):
-        """fp32 OIHW parameter -> packed compute-dtype matrix [rows_pad][ktot].
+        """fp32 OIHW parameter -> packed compute-dtype matrix [rows_pad][ktot], one launch.
         (row_off / k_off may be negative: elements that land outside [0, rows_pad) x [0, cin_pad) are skipped -- channel slices)"""
-        d = ConvDesc(dt, kh, kw, 0, cin_pad, rows_pad, 0, 0)
-        elems = self.L.dbx_conv_packed_elems(C.byref(d))
         if out is None:
-            out = torch.zeros(elems * _lib.ESIZE[dt], dtype=torch.uint8, device=w.device)
-        co, ci = w.shape[0], w.shape[1]
-        if self._defer is not None:       # table build: record the job, the multi-tensor launch does the work
-            es = _lib.ESIZE[dt]
-            ktot = (kh * kw * cin_pad * es + 127) // 128 * 128 // es
-            self._defer.append((w.data_ptr(), out.data_ptr(), co, ci, kh * kw, mode, rows_pad if mode >= 4 else ktot, cin_pad,
-                                row_off, k_off, rows_pad))
-            self._defer_keep.append(out)
-            return out
-        check(self.L.dbx_pack_weight(dt, mode, ptr(w.detach()), co, ci, kh, kw, ptr(out), rows_pad, cin_pad,
+            out = self._buffer(Image(None, (), dt, mode, kh, kw, rows_pad, cin_pad, ()), w.device)
+        check(self.L.dbx_pack_weight(dt, mode, ptr(w.detach()), w.shape[0], w.shape[1], kh, kw, ptr(out), rows_pad, cin_pad,
                                      row_off, k_off, stream_ptr()))
         return out
 
-    def _bias(self, names, pad_to):
-        ps = [self._param(n + '.bias') for n in names]
-        key = tuple(names)
-        ver = tuple((p._version, p.data_ptr()) for p in ps)
-        ent = self.bias_cache.get(key)
-        if ent is not None and (ent[0] == ver or key in self._table_keys):
-            return ent[1]
-        b = ent[1] if ent is not None else torch.zeros(pad_to, dtype=torch.float32, device=ps[0].device)
-        o = 0
-        for p in ps:
-            if self._defer is not None:
-                self._defer.append((p.data_ptr(), b.data_ptr(), p.numel(), 1, 1, 2, 0, 0, o, 0, 0))
-            else:
-                b[o:o + p.numel()].copy_(p.detach())
-            o += p.numel()
-        if self._defer is not None:
-            self._defer_keep.append(b)
-        self.bias_cache[key] = (ver, b)
-        return b
+    def _manifest(self, P):
+        """role -> Image for every packed weight / bias a step on plan P reads, in pack-table order; built once per plan (a plan is one dtype
+        and one mode).  The ONLY place that asks the layout questions -- which launches take fragment-order weights (_frag, _frag_heads), the
+        fused heads forward (_heads_fused), the heads' backward by linearity (_lin_bwd), the refine convs (DBX_REFINE_LINEAR=0: the plan
+        holds their buffers) -- so the pack table, the layout signature, the fused SGD step and the call sites cannot disagree.
+        forward_raw / backward_raw fetch by role (_fetch) and take CONV_WFRAG from the image's mode."""
+        if P.manifest is not None:
+            return P.manifest
+        dt, train, heads = P.dtype_id, P.train, _HEADS[self.kind]
+        nh = len(heads)
+        M = {}
 
-    def _w_fwd(self, dt, stem, cin_pad, cout_pad, frag=False):
-        """Packed forward weights; frag: MFMA-fragment order (pack mode 4) for the register-streamed-weights kernel."""
-        w = self._param(stem + '.weight')
-        mode = 4 if frag else 0
-        return self._packed((stem, mode, dt),
-                            lambda old: self._pack(dt, mode, w, cout_pad, cin_pad, w.shape[2], w.shape[3], out=old),
-                            (w._version, w.data_ptr()))
+        def weight(role, name, stems, mode, k, rows_pad, cin_pad, place=((0, 0),), idt=dt):
+            M[role] = Image((name, mode, idt), tuple(s + '.weight' for s in stems), idt, mode, k, k, rows_pad, cin_pad, tuple(place))
+
+        def bias(role, stems, pad_to, place=((0, 0),)):
+            M[role] = Image(tuple(stems), tuple(s + '.bias' for s in stems), dt, 2, 1, 1, pad_to, 0, tuple(place))
+        # a conv whose MaxPool2d(2, 2) runs in its epilogue (dbx_conv_forward_pool_idx: the 8-phase kernels) reads plain-order weights
+        P.pool_fused = {}
+        for stem in ('conv1_2_1', 'conv2_2_1', 'conv3_4_1'):
+            c = _CH[stem][0]
+            d = ConvDesc(dt, 3, 3, 1, c, c, _lib.EPI_BIAS | _lib.EPI_RELU, 0)
+            xv, yv = (self._view(P, nm) for nm in _FWD_IO[stem])
+            P.pool_fused[stem] = bool(self.L.dbx_conv_pool_fusable(C.byref(d), C.byref(xv), C.byref(yv)))
+        for stem, cin, cout in _BACKBONE:
+            frag = not P.pool_fused.get(stem) and self._frag(P, dt, stem, 'f')
+            weight((stem, 'f'), stem, [stem], 4 if frag else 0, 3, max(64, cout), P.cin0 if cin == 3 else cin)
+            bias((stem, 'bias'), [stem], max(64, cout))
+        h1, h2 = ['conv5_1_' + s for s, _ in heads], ['conv5_2_' + s for s, _ in heads]
+        cols = [(0, 512 * i) for i in range(nh)]                    # head i at K offset 512 i, rows 0..
+        if train:             # (eval runs the folded heads: _w_heads_folded, packed on its own)
+            diag = [(sum(k for _, k in heads[:i]), 512 * i) for i in range(nh)]
+            weight(('heads1', 'f'), 'heads1', h1, 4 if self._frag_heads(P, dt, 'f') else 0, 1, 512 * nh, 768, [(512 * i, 0) for i in range(nh)])
+            bias(('heads1', 'bias'), h1, 512 * nh, [(512 * i, 0) for i in range(nh)])
+            # stage 2 as one block-diagonal matrix [64 rows][512 nh]: head i's k_i rows at row sum(k_<i), columns 512 i ..
+            weight(('heads2', 'f'), 'heads2', h2, 0, 1, 64, 512 * nh, diag)
+            fk = self._heads_fused(P, dt)
+            if fk == 1:       # dbx_heads_forward_fused on the ws kernel: fragment order, 256 rows (it reads the first 32-row block of each 16-channel
+                weight(('heads2', 'fused'), 'heads2', h2, 4, 1, 256, 512 * nh, cols)             # column block), every head's rows at 0..
+            elif fk == 2:     # ... on the 8-phase kernel: plain order, every head's rows at 0.. (a lane's MFMA fragment is one 16-byte load)
+                weight(('heads2', 'fused'), 'heads2_rows0', h2, 0, 1, 64, 512 * nh, cols)
+            bias(('heads2', 'bias'), h2, 64, [(r, 0) for r, _ in diag])
+        # the refine branch runs from its fp32 parameters (folded 7x7 conv, dbx_refine_backward) unless DBX_REFINE_LINEAR=0 in training
+        rf_convs = 'rf_in' in P.B
+        if rf_convs:
+            for stem, k, cin_pad in (('conv6_1_det', 3, P.crf), ('conv6_2_det', 5, 64), ('conv6_3_det', 1, 64)):
+                weight((stem, 'f'), stem, [stem], 0, k, 64, cin_pad, idt=P.rdt)
+            for stem in ('conv6_1_det', 'conv6_2_det', 'conv6_3_det'):
+                bias((stem, 'bias'), [stem], 64)
+        if train:
+            # data-gradient images: rows = input channels, K = [flipped tap][output channel]
+            for stem, cin, cout in _BACKBONE[1:]:
+                weight((stem, 'b'), stem, [stem], 5 if self._frag(P, dt, stem, 'b') else 1, 3, max(64, cin), cout)
+            if self._lin_bwd(dt):
+                # one image per part of the fusion concat: rows = that part's input channels ('a': 0..511, the up-sampled conv4_4;
+                # 'c': 512..767, conv3_4), K = the 512 nh hidden channels of all heads
+                for part, rows, roff in (('a', 512, 0), ('c', 256, -512)):
+                    weight(('heads1', 'bwd_' + part), 'heads1_' + part, h1, 5 if self._frag_heads(P, dt, 'b' + part) else 1, 1, rows, 512 * nh,
+                           [(roff, k_off) for _, k_off in cols])
+            else:
+                weight(('heads1', 'bwd'), 'heads1', h1, 5 if self._frag_heads(P, dt, 'b') else 1, 1, 768, 512 * nh, cols)
+            if rf_convs:
+                for stem, k, cin_pad in (('conv6_3_det', 1, P.crf), ('conv6_2_det', 5, 64), ('conv6_1_det', 3, 64)):
+                    weight((stem, 'b'), stem, [stem], 1, k, 64, cin_pad)
+        P.manifest = M
+        P.lay = tuple(im for im in M.values() if im.mode == 2 or im.dt == dt)       # what the pack table holds (the table is one dtype)
+        return M
+
+    def _fetch(self, P, role, plain=False):
+        """(packed tensor, CONV_WFRAG or 0) of the image plan P's manifest names `role`.  plain=True: the plain-order image even where the
+        manifest holds the fragment-order one (a launch that cannot take it: injected dropout masks, the fused conv1_2 data gradient, a
+        GEMM over an on-demand d_hid).
+        The one rule for images outside the pack table -- those, and refine conv weights of another element type: they are built on demand
+        under their own key and re-packed whenever a source parameter's version moved.  Table images were refreshed by _prepare_weights()
+        at the top of forward and are handed out unchecked."""
+        im = self._manifest(P)[role]
+        if plain and im.mode >= 4:
+            im = im._replace(key=(im.key[0], im.mode - 4, im.key[2]), mode=im.mode - 4)
+        cache = self.bias_cache if im.mode == 2 else self.wcache
+        ent = cache.get(im.key)
+        if ent is None or im.key not in self._table_keys:
+            ps = [self._param(nm) for nm in im.srcs]
+            ver = tuple((p._version, p.data_ptr()) for p in ps)
+            if ent is None or ent[0] != ver:
+                out = ent[1] if ent is not None else self._buffer(im, ps[0].device)
+                for p, (row_off, k_off) in zip(ps, im.place):
+                    if im.mode == 2:
+                        out[row_off:row_off + p.numel()].copy_(p.detach())
+                    else:
+                        self._pack(im.dt, im.mode, p, im.rows_pad, im.cin_pad, im.kh, im.kw, out, row_off, k_off)
+                cache[im.key] = ent = (ver, out)
+        return ent[1], (_lib.CONV_WFRAG if im.mode >= 4 else 0)
+
+    def _prepare_weights(self, dt, train, P):
+        """Re-pack all parameters with ONE kernel launch when any of them changed (e.g. after an optimizer step)."""
+        params = [p for _, p in self.net.named_parameters()]
+        self._manifest(P)
+        lay = P.lay                    # the layout signature: the table's images themselves
+        sig = (dt, train, tuple((p._version, p.data_ptr()) for p in params), lay)
+        if sig == self._wsig:
+            return
+        tkey = (dt, train, lay, tuple(dp for _, dp in sig[2]))   # the table stores EVERY parameter's pointer
+        tab = self._tables.get(tkey)
+        if tab is None:
+            import numpy as np
+            self.wcache.clear(); self.bias_cache.clear()
+            dev, es, jobs = params[0].device, _lib.ESIZE[dt], []
+            for im in lay:
+                out = self._buffer(im, dev)
+                ps = [self._param(nm) for nm in im.srcs]
+                (self.bias_cache if im.mode == 2 else self.wcache)[im.key] = (tuple((p._version, p.data_ptr()) for p in ps), out)
+                ktot = (im.kh * im.kw * im.cin_pad * es + 127) // 128 * 128 // es
+                for p, (row_off, k_off) in zip(ps, im.place):
+                    if im.mode == 2:
+                        jobs.append(PackJob(p.data_ptr(), out.data_ptr(), p.numel(), 1, 1, 2, 0, 0, row_off, 0, 0))
+                    else:
+                        jobs.append(PackJob(p.data_ptr(), out.data_ptr(), p.shape[0], p.shape[1], im.kh * im.kw, im.mode,
+                                            im.rows_pad if im.mode >= 4 else ktot, im.cin_pad, row_off, k_off, im.rows_pad))
+            self._table_keys = {im.key for im in lay}
+            rec = np.zeros(len(jobs), dtype=[(f, '<u8' if f in ('src', 'dst') else '<i8' if f == 'ktot' else '<i4') for f in PackJob._fields])
+            assert rec.dtype.itemsize == 56
+            for i, j in enumerate(jobs):
+                rec[i] = tuple(j)
+            tab = (torch.from_numpy(rec.view(np.uint8).copy()).to(dev), len(jobs), max(j.co * j.ci * j.taps for j in jobs), jobs)
+            self._tables = {tkey: tab}
+            self._sgd_tables = {}
+        check(self.L.dbx_pack_multi(dt, ptr(tab[0]), tab[1], tab[2], stream_ptr()))
+        self._wsig = sig
+        if train:
+            # optim.SGD.step() finds the engine through its parameters and folds the NEXT re-packing into the update (sgd_pack_step)
+            self._last_prep = (dt, tkey, lay)
+            register_params(self, params)
 
     def conv_plan(self, dt, x, y, kh, kw, cpad, cin_pad, cout_pad, epi):
         """The library's kernel choice for this problem (dbx_conv_plan): (ConvPlan.kernel, name, wants fragment-order weights)."""
@@ -322,170 +443,38 @@ class Engine:
             self._plans_conv[key] = ent
         return ent
 
-    def _w_heads1(self, dt, frag=False):
-        heads = _HEADS[self.kind]
-        ws = [self._param('conv5_1_%s.weight' % s) for s, _ in heads]
-        mode = 4 if frag else 0
-
-        def build(out):
-            for i, w in enumerate(ws):
-                out = self._pack(dt, mode, w, 512 * len(ws), 768, 1, 1, out=out, row_off=512 * i)
-            return out
-        return self._packed(('heads1', mode, dt), build, tuple((w._version, w.data_ptr()) for w in ws))
-
-    def _w_heads2(self, dt):
-        """Stage-2 head weights as one block-diagonal matrix [64 rows][512 nh]: head i's k_i rows at row sum(k_<i), columns 512 i .."""
-        heads = _HEADS[self.kind]
-        ws = [self._param('conv5_2_%s.weight' % s) for s, _ in heads]
-
-        def build(out):
-            r = 0
-            for i, (w, (_, k)) in enumerate(zip(ws, heads)):
-                out = self._pack(dt, 0, w, 64, 512 * len(ws), 1, 1, out=out, row_off=r, k_off=512 * i)
-                r += k
-            return out
-        return self._packed(('heads2', 0, dt), build, tuple((w._version, w.data_ptr()) for w in ws))
-
-    def _w_heads2_frag(self, dt):
-        """Stage-2 head weights in MFMA-fragment order for the fused heads forward (dbx_heads_forward_fused): one mode-4 image of 256 rows
-        x 512 nh columns, head i's k_i rows at rows 0.. and columns 512 i.. (the kernel only reads the first 32-row block of each 16-channel
-        column block)."""
-        heads = _HEADS[self.kind]
-        ws = [self._param('conv5_2_%s.weight' % s) for s, _ in heads]
-
-        def build(out):
-            for i, w in enumerate(ws):
-                out = self._pack(dt, 4, w, 256, 512 * len(ws), 1, 1, out=out, row_off=0, k_off=512 * i)
-            return out
-        return self._packed(('heads2', 4, dt), build, tuple((w._version, w.data_ptr()) for w in ws))
-
-    def _w_heads2_rows0(self, dt):
-        """Stage-2 head weights for the fused heads forward on the 8-phase kernel: one plain (mode 0) image of 64 rows x 512 nh columns, head
-        i's k_i rows at rows 0.. and columns 512 i.. -- a lane's MFMA fragment (row = output, eight consecutive hidden channels) is one
-        16-byte load."""
-        heads = _HEADS[self.kind]
-        ws = [self._param('conv5_2_%s.weight' % s) for s, _ in heads]
-
-        def build(out):
-            for i, w in enumerate(ws):
-                out = self._pack(dt, 0, w, 64, 512 * len(ws), 1, 1, out=out, row_off=0, k_off=512 * i)
-            return out
-        return self._packed(('heads2', 'rows0', dt), build, tuple((w._version, w.data_ptr()) for w in ws))
-
+    # The layout questions below are asked by _manifest() alone, once per plan.
     def _heads_fused(self, P, dt):
         """Both 1x1 convs of the heads in one kernel (dbx_heads_forward_fused)?  16-bit training plans whose 768 -> 512 nh GEMM runs on the
-        register-streamed-weights kernel with hash dropout; DBX_HEADS_FUSED=0 keeps the two GEMMs (A/B, tests)."""
-        key = ('heads2', 'fused')
-        r = P.frag.get(key)
-        if r is None:
-            heads = _HEADS[self.kind]
-            nh = len(heads)
-            r = 0           # 0: two GEMMs; 1: fused on the ws kernel (fragment-order weights); 2: fused on the 8-phase kernel (plain weights)
-            if P.train and dt != _lib.F32 and os.environ.get('DBX_HEADS_FUSED', '1') != '0':
-                d = ConvDesc(dt, 1, 1, 0, 768, 512 * nh, _lib.EPI_BIAS | _lib.EPI_DROPHASH, 0)
-                ks = (C.c_int32 * nh)(*[k for _, k in heads])
-                r = int(self.L.dbx_heads_forward_fusable(C.byref(d), C.byref(P.B['fusion'].view()), C.byref(P.B['hid'].view()), ks, nh))
-            P.frag[key] = r
-        return r
+        register-streamed-weights kernel with hash dropout; DBX_HEADS_FUSED=0 keeps the two GEMMs (A/B, tests).
+        0: two GEMMs; 1: fused on the ws kernel (fragment-order weights); 2: fused on the 8-phase kernel (plain weights)"""
+        heads = _HEADS[self.kind]
+        nh = len(heads)
+        if not P.train or dt == _lib.F32 or os.environ.get('DBX_HEADS_FUSED', '1') == '0':
+            return 0
+        d = ConvDesc(dt, 1, 1, 0, 768, 512 * nh, _lib.EPI_BIAS | _lib.EPI_DROPHASH, 0)
+        ks = (C.c_int32 * nh)(*[k for _, k in heads])
+        return int(self.L.dbx_heads_forward_fusable(C.byref(d), C.byref(P.B['fusion'].view()), C.byref(P.B['hid'].view()), ks, nh))
 
     def _frag_heads(self, P, dt, which):
-        """Fragment-order weights for the heads' 768 -> 512 nh GEMM ('f') / its split-destination data gradient ('b')?"""
-        key = ('heads1', which)
-        r = P.frag.get(key)
-        if r is None:
-            B, nh = P.B, len(_HEADS[self.kind])
-            if which == 'f':
-                r = self.conv_plan(dt, B['fusion'].view(), B['hid'].view(), 1, 1, 0, 768, 512 * nh, _lib.EPI_BIAS | _lib.EPI_DROPHASH)[2]
-            elif which == 'ba' and 'd_g44' in B and dt != _lib.F32:
-                r = self.conv_plan(dt, B['d_g44'].view(), B['d_a44'].view(), 1, 1, 0, 512 * nh, 512, _lib.EPI_GATE)[2]
-            elif which == 'bc' and getattr(P, 'heads_gen', False):
-                r = dt != _lib.F32                         # dbx_heads1_dgrad_gen takes the fragment-order image (its fp32 reference form the plain one)
-            elif which == 'bc' and 'd_hid' in B and dt != _lib.F32:
-                r = self.conv_plan(dt, B['d_hid'].view(), B['d_c34'].view(), 1, 1, 0, 512 * nh, 256, _lib.EPI_GATE)[2]
-            elif which in ('ba', 'bc'):
-                r = False
-            elif 'd_hid' in B and 'd_ups' in B and dt != _lib.F32:
-                dv = B['d_ups'].view()
-                both = View(dv.ptr, dv.n, dv.h, dv.w, dv.pad, 768, 0, 768)      # both destinations' couts, for planning only
-                r = self.conv_plan(dt, B['d_hid'].view(), both, 1, 1, 0, 512 * nh, 768, 0)[2]
-            else:
-                r = False
-            P.frag[key] = r
-        return r
-
-    def _weight_getters(self, dt, train, P):
-        """Touch every packed weight / bias the step uses (same calls as forward_raw / backward_raw make)."""
-        kind = self.kind
-        heads = _HEADS[kind]
-        nh = len(heads)
-        for stem, cin, cout in _BACKBONE:
-            self._w_fwd(dt, stem, P.cin0 if cin == 3 else cin, max(64, cout), frag=self._frag(P, dt, stem, 'f'))
-            self._bias([stem], max(64, cout))
-        if train:             # (eval runs the folded heads: _w_heads_folded, packed on its own)
-            self._w_heads1(dt, frag=self._frag_heads(P, dt, 'f'))
-            self._bias(['conv5_1_' + s_ for s_, _ in heads], 512 * nh)
-            self._w_heads2(dt)
-            if self._heads_fused(P, dt) == 1:
-                self._w_heads2_frag(dt)
-            elif self._heads_fused(P, dt) == 2:
-                self._w_heads2_rows0(dt)
-            self._bias(['conv5_2_' + s_ for s_, _ in heads], 64)
-        # the refine branch runs from its fp32 parameters (folded 7x7 conv, dbx_refine_backward) unless DBX_REFINE_LINEAR=0 in training
-        rf_convs = kind != 'DenseBox' and train and os.environ.get('DBX_REFINE_LINEAR', '1') == '0'
-        if rf_convs:
-            if P.rdt == dt:       # (the table is one dtype)
-                self._w_fwd(dt, 'conv6_1_det', P.crf, 64)
-                self._w_fwd(dt, 'conv6_2_det', 64, 64)
-                self._w_fwd(dt, 'conv6_3_det', 64, 64)
-            self._bias(['conv6_1_det'], 64); self._bias(['conv6_2_det'], 64); self._bias(['conv6_3_det'], 64)
-        if train:
-            for stem, cin, cout in _BACKBONE[1:]:
-                self._w_bwd(dt, stem, max(64, cin), cout, frag=self._frag(P, dt, stem, 'b'))
-            if self._lin_bwd(dt):
-                self._w_heads1_bwd_part(dt, 'a', frag=self._frag_heads(P, dt, 'ba'))
-                self._w_heads1_bwd_part(dt, 'c', frag=self._frag_heads(P, dt, 'bc'))
-            else:
-                self._w_heads1_bwd(dt, frag=self._frag_heads(P, dt, 'b'))
-            if rf_convs:
-                self._w_bwd(dt, 'conv6_3_det', 64, P.crf)
-                self._w_bwd(dt, 'conv6_2_det', 64, 64)
-                self._w_bwd(dt, 'conv6_1_det', 64, 64)
-
-    def _prepare_weights(self, dt, train, P):
-        """Re-pack all parameters with ONE kernel launch when any of them changed (e.g. after an optimizer step)."""
-        params = [p for _, p in self.net.named_parameters()]
-        lay = tuple(self._frag(P, dt, st, wh) for st, _, _ in _BACKBONE for wh in ('f', 'b'))   # layouts the kernels of this plan want
-        if train:
-            lay += (self._heads_fused(P, dt),)
-            lay += (self._frag_heads(P, dt, 'f'),) + ((self._frag_heads(P, dt, 'ba'), self._frag_heads(P, dt, 'bc')) if self._lin_bwd(dt)
-                                                      else (self._frag_heads(P, dt, 'b'),))
-        sig = (dt, train, tuple((p._version, p.data_ptr()) for p in params), lay)
-        if sig == self._wsig:
-            return
-        tkey = (dt, train, P.cin0, P.crf, lay, tuple(dp for _, dp in sig[2]))   # the table stores EVERY parameter's pointer
-        tab = self._tables.get(tkey)
-        if tab is None:
-            import numpy as np
-            self._defer, keys_before = [], set(self.wcache) | set(self.bias_cache)
-            self.wcache.clear(); self.bias_cache.clear(); self._table_keys = set()
-            self._weight_getters(dt, train, P)
-            jobs, self._defer = self._defer, None
-            self._table_keys = set(self.wcache) | set(self.bias_cache)
-            rec = np.zeros(len(jobs), dtype=[('src', '<u8'), ('dst', '<u8'), ('co', '<i4'), ('ci', '<i4'), ('taps', '<i4'),
-                                             ('mode', '<i4'), ('ktot', '<i8'), ('cin_pad', '<i4'), ('row_off', '<i4'),
-                                             ('k_off', '<i4'), ('rows_lim', '<i4')])
-            for i, j in enumerate(jobs):
-                rec[i] = j
-            dev = params[0].device
-            tab = (torch.from_numpy(rec.view(np.uint8).copy()).to(dev), len(jobs), max(j[2] * j[3] * j[4] for j in jobs), jobs)
-            self._tables = {tkey: tab}
-            self._sgd_tables = {}
-        check(self.L.dbx_pack_multi(dt, ptr(tab[0]), tab[1], tab[2], stream_ptr()))
-        self._wsig = sig
-        if train:
-            # optim.SGD.step() finds the engine through its parameters and folds the NEXT re-packing into the update (sgd_pack_step)
-            self._last_prep = (dt, tkey, lay)
-            register_params(self, params)
+        """Fragment-order weights for the heads' 768 -> 512 nh GEMM ('f') / its data gradient: 'ba' / 'bc' = the two parts of the concat under
+        the backward by linearity, 'b' = the split-destination GEMM over both?"""
+        B, nh = P.B, len(_HEADS[self.kind])
+        if which == 'f':
+            return self.conv_plan(dt, B['fusion'].view(), B['hid'].view(), 1, 1, 0, 768, 512 * nh, _lib.EPI_BIAS | _lib.EPI_DROPHASH)[2]
+        if dt == _lib.F32:
+            return False
+        if which == 'ba':
+            return 'd_g44' in B and self.conv_plan(dt, B['d_g44'].view(), B['d_a44'].view(), 1, 1, 0, 512 * nh, 512, _lib.EPI_GATE)[2]
+        if which == 'bc':
+            if P.heads_gen:
+                return True                                # dbx_heads1_dgrad_gen takes the fragment-order image (its fp32 reference form the plain one)
+            return 'd_hid' in B and self.conv_plan(dt, B['d_hid'].view(), B['d_c34'].view(), 1, 1, 0, 512 * nh, 256, _lib.EPI_GATE)[2]
+        if 'd_hid' not in B or 'd_ups' not in B:
+            return False
+        dv = B['d_ups'].view()
+        both = View(dv.ptr, dv.n, dv.h, dv.w, dv.pad, 768, 0, 768)      # both destinations' couts, for planning only
+        return self.conv_plan(dt, B['d_hid'].view(), both, 1, 1, 0, 512 * nh, 768, 0)[2]
 
     def sgd_pack_step(self, live, ptrs, lr, momentum, weight_decay, first, guard=None, step_id=0):
         """optim.SGD.step() with this engine's re-packing folded in (dbx_sgd_pack_step): one job per parameter updates it and emits the packed
@@ -512,28 +501,23 @@ class Engine:
             return False                                  # (this configuration does not fit the fused kernel: decided once, not per step)
         if st is None:
             import numpy as np
-            by_src, order = {}, []
-            for j in tab[3]:                              # (src, dst, co, ci, taps, mode, ktot, cin_pad, row_off, k_off, rows_lim)
-                if j[0] not in by_src:
-                    by_src[j[0]] = []
-                    order.append(j[0])
-                by_src[j[0]].append(j)
+            by_src = {}                                   # source parameter -> its pack jobs, in table order
+            for j in tab[3]:
+                by_src.setdefault(j.src, []).append(j)
             es = _lib.ESIZE[dt]
             recs = []
-            for src in order:
-                js = by_src[src]
+            for src, js in by_src.items():
                 if src not in pidx:
                     continue                              # no gradient: unchanged, its packed copies stay valid
-                if len(js) > 4 or len({(j[2], j[3], j[4]) for j in js}) != 1:
+                j0 = js[0]
+                if len(js) > 4 or any((j.co, j.ci, j.taps) != (j0.co, j0.ci, j0.taps) for j in js):
                     self._sgd_tables[skey] = False
                     return False
-                co, ci, taps = js[0][2], js[0][3], js[0][4]
-                tiled = es == 2 and taps <= 25 and all(
-                    j[5] != 2 and (ci if j[5] in (0, 4) else co) % 8 == 0 and j[9] % 8 == 0 and j[7] % 8 == 0 for j in js)
-                recs.append((src, pidx[src], co, ci, taps, len(js), int(tiled), js))
-            packed = set(order)
+                tiled = es == 2 and j0.taps <= 25 and all(
+                    j.mode != 2 and (j.ci if j.mode in (0, 4) else j.co) % 8 == 0 and j.k_off % 8 == 0 and j.cin_pad % 8 == 0 for j in js)
+                recs.append((src, pidx[src], j0.co, j0.ci, j0.taps, len(js), int(tiled), js))
             for p in live:                                # parameters nobody packs (the folded refine convs): plain update
-                if p.data_ptr() not in packed:
+                if p.data_ptr() not in by_src:
                     recs.append((p.data_ptr(), pidx[p.data_ptr()], p.numel(), 1, 1, 0, 0, []))
             dst_t = [('dst', '<u8'), ('ktot', '<i8'), ('mode', '<i4'), ('cin_pad', '<i4'), ('row_off', '<i4'), ('k_off', '<i4'),
                      ('rows_lim', '<i4'), ('pad', '<i4')]
@@ -544,7 +528,7 @@ class Engine:
                 rec[i]['p'], rec[i]['pidx'], rec[i]['co'], rec[i]['ci'], rec[i]['taps'] = src, pi, co, ci, taps
                 rec[i]['ndst'], rec[i]['tiled'] = nd, tiled
                 for k, j in enumerate(js):
-                    rec[i]['d'][k] = (j[1], j[6], j[5], j[7], j[8], j[9], j[10], 0)
+                    rec[i]['d'][k] = (j.dst, j.ktot, j.mode, j.cin_pad, j.row_off, j.k_off, j.rows_lim, 0)
             st = (torch.from_numpy(rec.view(np.uint8).copy()).to(params[0].device), len(recs), max(r[2] * r[3] * r[4] for r in recs))
             if len(self._sgd_tables) >= 8:                  # (a caller cycling through many live-parameter sets: keep the cache small)
                 self._sgd_tables.pop(next(iter(self._sgd_tables)))
@@ -579,12 +563,10 @@ class Engine:
                                         C.c_void_p(wf.data_ptr() + o * 768 * 4), C.c_void_p(bf.data_ptr() + o * 4),
                                         stream_ptr()))
             o += k
-        saved, self._defer = self._defer, None          # pack immediately (not part of the multi-tensor table)
-        wp = self._pack(dt, 0, wf, 64, 768, 1, 1)
+        wp = self._pack(dt, 0, wf, 64, 768, 1, 1)       # (packed on its own: not part of the multi-tensor table)
         # the two halves of the concat separately (eval by linearity: the conv4_4 part runs on conv4_4's own grid)
         wpa = self._pack(dt, 0, wf[:, :512].contiguous(), 64, 512, 1, 1)
         wpc = self._pack(dt, 0, wf[:, 512:].contiguous(), 64, 256, 1, 1)
-        self._defer = saved
         self.wcache[('folded', dt)] = (ver, (wp, bf, ktot, wpa, wpc))
         return wp, bf, ktot, wpa, wpc
 
@@ -611,28 +593,25 @@ class Engine:
         return wf, bf, vf
 
     # ------------------------------------------------------------------ plumbing
+    @staticmethod
+    def _view(P, name):
+        """The view behind a buffer name of _FWD_IO / _BWD_IO ('c34' = conv3_4's channels of the fusion tensor)."""
+        return P.B['fusion'].view(512, 256) if name == 'c34' else P.B[name].view()
+
     def _frag(self, P, dt, stem, which):
         """Does the library run this backbone layer's forward ('f') / data-gradient ('b') conv with fragment-order weights
         (the register-streamed-weights kernel) under plan P?  Decided by dbx_conv_plan on the very views the call uses."""
-        key = (stem, which)
-        r = P.frag.get(key)
-        if r is None:
-            B = P.B
-            cin, cout = _CH[stem]
-
-            def vw(name):
-                return B['fusion'].view(512, 256) if name == 'c34' else B[name].view()
-            if which == 'f':
-                src, dst = _FWD_IO[stem]
-                cin_pad = P.cin0 if cin == 3 else cin
-                r = self.conv_plan(dt, vw(src), vw(dst), 3, 3, 1, cin_pad, max(64, cout), _lib.EPI_BIAS | _lib.EPI_RELU)[2]
-            else:
-                dz, dx = _BWD_IO.get(stem, (None, None))           # conv1_1 has no data gradient
-                # the epilogue of the real call: ReLU-gated, except the data gradients that feed a pooling layer (conv2_1, conv3_1, conv4_1)
-                gated = stem not in ('conv2_1_1', 'conv3_1_1', 'conv4_1_1')
-                r = self.conv_plan(dt, vw(dz), vw(dx), 3, 3, 1, cout, max(64, cin), _lib.EPI_GATE if gated else 0)[2] if dz in B else False
-            P.frag[key] = r
-        return r
+        cin, cout = _CH[stem]
+        if which == 'f':
+            src, dst = _FWD_IO[stem]
+            return self.conv_plan(dt, self._view(P, src), self._view(P, dst), 3, 3, 1, P.cin0 if cin == 3 else cin, max(64, cout),
+                                  _lib.EPI_BIAS | _lib.EPI_RELU)[2]
+        dz, dx = _BWD_IO.get(stem, (None, None))           # conv1_1 has no data gradient
+        if dz not in P.B:
+            return False
+        # the epilogue of the real call: ReLU-gated, except the data gradients that feed a pooling layer (conv2_1, conv3_1, conv4_1)
+        gated = stem not in ('conv2_1_1', 'conv3_1_1', 'conv4_1_1')
+        return self.conv_plan(dt, self._view(P, dz), self._view(P, dx), 3, 3, 1, cout, max(64, cin), _lib.EPI_GATE if gated else 0)[2]
 
     def _next_drop_seed(self):
         """Per-step seed of the counter-based dropout hash.  The stream starts from torch.initial_seed() (torch.manual_seed
@@ -662,22 +641,21 @@ class Engine:
             self.plans = {key: p}      # keep one plan alive (shape changes re-plan)
         return p
 
+    def _timed(self, name, flops):
+        """Context manager around the launches of one profile entry: with profiling on, brackets them with HIP events and appends {kernel,
+        flops, start, end}.  `name` may be a callable: asked behind the launch, and only when profiling (dbx_conv_plan, or a name the body
+        decides)."""
+        return _NOT_TIMED if self.profile is None else _Timed(self.profile, name, flops)
+
     def _conv(self, dt, x, y, wpk, bias, kh, kw, cpad, cin_pad, cout_pad, epi, gate=None, dropmask=None, dm_ld=0,
               alg_ci=None, drop_seed=0):
         d = ConvDesc(dt, kh, kw, cpad, cin_pad, cout_pad, epi, drop_seed)
-        prof = self.profile
-        if prof is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        check(self.L.dbx_conv_forward(C.byref(d), C.byref(x), ptr(wpk), ptr(bias), C.byref(y),
-                                      C.byref(gate) if gate is not None else None,
-                                      C.c_void_p(dropmask) if dropmask else None, dm_ld, stream_ptr()))
-        if prof is not None:
-            ev1.record()
-            # the kernel the library selected (dbx_conv_plan), algorithmic FLOP = 2 * pixels * taps * Cin * Cout (real)
-            name = self.conv_plan(dt, x, y, kh, kw, cpad, cin_pad, cout_pad, epi)[1]
-            ci = alg_ci if alg_ci is not None else cin_pad
-            prof.append({'kernel': name, 'flops': 2.0 * y.n * y.h * y.w * kh * kw * ci * y.c, 'start': ev0, 'end': ev1})
+        # the kernel the library selected (dbx_conv_plan), algorithmic FLOP = 2 * pixels * taps * Cin * Cout (real)
+        with self._timed(lambda: self.conv_plan(dt, x, y, kh, kw, cpad, cin_pad, cout_pad, epi)[1],
+                         2.0 * y.n * y.h * y.w * kh * kw * (alg_ci if alg_ci is not None else cin_pad) * y.c):
+            check(self.L.dbx_conv_forward(C.byref(d), C.byref(x), ptr(wpk), ptr(bias), C.byref(y),
+                                          C.byref(gate) if gate is not None else None,
+                                          C.c_void_p(dropmask) if dropmask else None, dm_ld, stream_ptr()))
 
     # ------------------------------------------------------------------ forward
     def forward(self, X):
@@ -733,11 +711,9 @@ class Engine:
 
         def conv3(stem, src, dst, cin, cout, dst_view=None):
             cin_pad = P.cin0 if cin == 3 else cin
-            frag = self._frag(P, dt, stem, 'f')
-            wp = self._w_fwd(dt, stem, cin_pad, max(64, cout), frag=frag)
+            wp, wfrag = self._fetch(P, (stem, 'f'))
             self._conv(dt, B[src].view(), dst_view if dst_view is not None else B[dst].view(), wp,
-                       self._bias([stem], max(64, cout)), 3, 3, 1, cin_pad, max(64, cout),
-                       RELU | (_lib.CONV_WFRAG if frag else 0), alg_ci=cin)
+                       self._fetch(P, (stem, 'bias'))[0], 3, 3, 1, cin_pad, max(64, cout), RELU | wfrag, alg_ci=cin)
 
         PI = P.pool_idx
 
@@ -747,51 +723,28 @@ class Engine:
             else:
                 check(L.dbx_maxpool2x2(dt, C.byref(xv), C.byref(yv), s))
 
-        conv3('conv1_1_1', 'x0', 'a11', 3, 64)
-        hook('a11')
-        d12 = ConvDesc(dt, 3, 3, 1, 64, 64, RELU, 0)
-        a11v, a12v, p1v = B['a11'].view(), B['a12'].view(), B['p1'].view()
-        if L.dbx_conv_pool_fusable(C.byref(d12), C.byref(a11v), C.byref(a12v)):
-            # conv1_2 + pool1 in one kernel; the full-resolution map is only kept when a backward pass will read it
-            prof = self.profile
-            if prof is not None:
-                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ev0.record()
-            # training without the nibbles (DBX_POOL_IDX=0): pool1's backward re-reads the full map, so it is written
-            check(L.dbx_conv_forward_pool_idx(C.byref(d12), C.byref(a11v), ptr(self._w_fwd(dt, 'conv1_2_1', 64, 64, frag=False)),
-                                              ptr(self._bias(['conv1_2_1'], 64)), C.byref(a12v), C.byref(p1v),
-                                              1 if (train and PI is None) else 0, ptr(PI['a12']) if PI else None, s))
-            if prof is not None:
-                ev1.record()
-                prof.append({'kernel': self.conv_plan(dt, a11v, a12v, 3, 3, 1, 64, 64, RELU)[1],
-                             'flops': 2.0 * a12v.n * a12v.h * a12v.w * 9 * 64 * 64, 'start': ev0, 'end': ev1})
-        else:
-            if P.a12_alias:                                  # (the plan's alias rule and the library's fusability rule must agree: never an assert)
-                raise RuntimeError('conv1_2 + pool1 not fusable on a plan without a full-resolution conv1_2 map')
-            conv3('conv1_2_1', 'a11', 'a12', 64, 64)
-            pool(a12v, p1v, 'a12')
-        hook('p1')              # (rounding commutes with the max: the pooled map stands for conv1_2's output)
         def conv3_pool(stem, src, yv, pv, c, key, keep_full):
             """3x3 conv + bias + ReLU with the following MaxPool2d(2, 2) in the 8-phase kernels' epilogue when the library takes it (16-bit,
-            even H, W): the pooling kernel's re-read of the map goes away, and so does the map itself when nothing else reads it (a22:
-            its other reader was pool2's backward, which reads the nibbles)."""
-            d = ConvDesc(dt, 3, 3, 1, c, c, RELU, 0)
-            xv = B[src].view()
-            if not L.dbx_conv_pool_fusable(C.byref(d), C.byref(xv), C.byref(yv)):
+            even H, W; asked when the plan's manifest was built, which then holds the plain-order image): the pooling kernel's re-read of
+            the map goes away, and so does the map itself when nothing else reads it (a12, a22: their other reader was the pooling's
+            backward, which reads the nibbles)."""
+            if not P.pool_fused[stem]:
+                if stem == 'conv1_2_1' and P.a12_alias:      # (the plan's alias rule and the library's fusability rule must agree: never an assert)
+                    raise RuntimeError('conv1_2 + pool1 not fusable on a plan without a full-resolution conv1_2 map')
                 conv3(stem, src, None, c, c, dst_view=yv)
                 pool(yv, pv, key)
                 return
-            prof = self.profile
-            if prof is not None:
-                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ev0.record()
-            check(L.dbx_conv_forward_pool_idx(C.byref(d), C.byref(xv), ptr(self._w_fwd(dt, stem, c, c, frag=False)), ptr(self._bias([stem], c)),
-                                              C.byref(yv), C.byref(pv), 1 if keep_full else 0, ptr(PI[key]) if PI else None, s))
-            if prof is not None:
-                ev1.record()
-                prof.append({'kernel': self.conv_plan(dt, xv, yv, 3, 3, 1, c, c, RELU)[1],
-                             'flops': 2.0 * yv.n * yv.h * yv.w * 9 * c * c, 'start': ev0, 'end': ev1})
+            d = ConvDesc(dt, 3, 3, 1, c, c, RELU, 0)
+            xv = B[src].view()
+            with self._timed(lambda: self.conv_plan(dt, xv, yv, 3, 3, 1, c, c, RELU)[1], 2.0 * yv.n * yv.h * yv.w * 9 * c * c):
+                check(L.dbx_conv_forward_pool_idx(C.byref(d), C.byref(xv), ptr(self._fetch(P, (stem, 'f'))[0]), ptr(self._fetch(P, (stem, 'bias'))[0]),
+                                                  C.byref(yv), C.byref(pv), 1 if keep_full else 0, ptr(PI[key]) if PI else None, s))
 
+        conv3('conv1_1_1', 'x0', 'a11', 3, 64)
+        hook('a11')
+        # conv1_2's full-resolution map is kept only when a backward pass will read it: training without the nibbles (DBX_POOL_IDX=0)
+        conv3_pool('conv1_2_1', 'a11', B['a12'].view(), B['p1'].view(), 64, 'a12', train and PI is None)
+        hook('p1')              # (rounding commutes with the max: the pooled map stands for conv1_2's output)
         conv3('conv2_1_1', 'p1', 'a21', 64, 128)
         hook('a21')
         # the full conv2_2 map is read by pool2's backward only when the nibbles are off (DBX_POOL_IDX=0)
@@ -855,54 +808,49 @@ class Engine:
             elif P.drop_active:
                 dm = self._fill_dropout(P, heads)       # injected masks (parity tests)
                 epi |= _lib.EPI_DROPMASK
-            hfrag = (epi & _lib.EPI_DROPMASK) == 0 and self._frag_heads(P, dt, 'f')
+            w1, w1frag = self._fetch(P, ('heads1', 'f'), plain=dm is not None)       # (the masked GEMM takes plain-order weights)
             ktot = sum(k for _, k in heads)
             big = None
-            b1 = self._bias(['conv5_1_' + s_ for s_, _ in heads], 512 * nh)
-            b2 = self._bias(['conv5_2_' + s_ for s_, _ in heads], 64)
-            fk = self._heads_fused(P, dt) if (P.drop_hash and not (epi & _lib.EPI_DROPMASK)) else 0
-            if fk == 1 and not hfrag:
-                fk = 0
-            if fk:
+            b1, b2 = self._fetch(P, ('heads1', 'bias'))[0], self._fetch(P, ('heads2', 'bias'))[0]
+            # the fused heads forward needs hash dropout, and on the ws kernel (fragment-order second image) a fragment-order first image
+            fused = P.manifest.get(('heads2', 'fused')) if P.drop_hash else None
+            if fused is not None and fused.mode == 4 and not w1frag:
+                fused = None
+            if fused is not None:
                 # both 1x1 convs of every head in one pass: the second (512 -> k) runs on the hidden tile while it is in registers;
                 # the 944 MB hidden map is written for the backward pass but not read back (dbx_heads_forward_fused)
                 need = L.dbx_heads_forward_fused_scratch_bytes(nh, n * h4 * w4)
                 if getattr(self, '_hf_scratch', None) is None or self._hf_scratch.numel() < need:
                     self._hf_scratch = torch.empty(int(need), dtype=torch.uint8, device=dev)
-                d = ConvDesc(dt, 1, 1, 0, 768, 512 * nh, epi | (_lib.CONV_WFRAG if fk == 1 else 0), P.drop_seed)
-                prof = self.profile
-                if prof is not None:
-                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    ev0.record()
+                w2f, w2frag = self._fetch(P, ('heads2', 'fused'))
+                if not w2frag:                          # (the 8-phase kernel: both images in plain order)
+                    w1 = self._fetch(P, ('heads1', 'f'), plain=True)[0]
+                d = ConvDesc(dt, 1, 1, 0, 768, 512 * nh, epi | w2frag, P.drop_seed)
                 # every head's own contiguous [N][k][H][W] tensor, as the reference returns them (no slice copies)
                 for stem, k in heads:
                     outs[stem] = torch.empty((n, k, h4, w4), dtype=torch.float32, device=dev)
-                check(L.dbx_heads_forward_fused_heads(C.byref(d), C.byref(B['fusion'].view()), ptr(self._w_heads1(dt, frag=fk == 1)), ptr(b1),
-                                                      C.byref(B['hid'].view()), ptr(self._w_heads2_frag(dt) if fk == 1 else self._w_heads2_rows0(dt)), ptr(b2),
-                                                      (C.c_int32 * nh)(*[k for _, k in heads]), nh,
-                                                      (C.c_void_p * nh)(*[outs[stem].data_ptr() for stem, _ in heads]), ptr(self._hf_scratch), s))
-                if prof is not None:
-                    ev1.record()
-                    prof.append({'kernel': ('conv3x3_ws_kernel<%s,1,1,2>' if fk == 1 else 'conv3x3_p8_kernel<%s,1,1>') % ('f16', 'bf16', 'f32')[dt],
-                                 'flops': 2.0 * n * h4 * w4 * (768 * 512 * nh + 512 * ktot), 'start': ev0, 'end': ev1})
+                with self._timed(('conv3x3_ws_kernel<%s,1,1,2>' if w2frag else 'conv3x3_p8_kernel<%s,1,1>') % _TNAME[dt],
+                                 2.0 * n * h4 * w4 * (768 * 512 * nh + 512 * ktot)):
+                    check(L.dbx_heads_forward_fused_heads(C.byref(d), C.byref(B['fusion'].view()), ptr(w1), ptr(b1), C.byref(B['hid'].view()),
+                                                          ptr(w2f), ptr(b2), (C.c_int32 * nh)(*[k for _, k in heads]), nh,
+                                                          (C.c_void_p * nh)(*[outs[stem].data_ptr() for stem, _ in heads]), ptr(self._hf_scratch), s))
             else:
-                self._conv(dt, B['fusion'].view(), B['hid'].view(), self._w_heads1(dt, frag=hfrag), b1, 1, 1, 0, 768, 512 * nh,
-                           epi | (_lib.CONV_WFRAG if hfrag else 0),
+                self._conv(dt, B['fusion'].view(), B['hid'].view(), w1, b1, 1, 1, 0, 768, 512 * nh, epi | w1frag,
                            dropmask=dm, dm_ld=512 * nh, drop_seed=P.drop_seed if P.drop_hash else 0)
                 # stage 2: the nh Conv1x1(512 -> k) as ONE block-diagonal GEMM 512 nh -> sum(k) over the full hidden rows (4 KiB contiguous
                 # per pixel instead of four strided 1-KiB slices in four launches); the heads' outputs are channel ranges of one tensor
                 big = torch.empty((n, ktot, h4, w4), dtype=torch.float32, device=dev)
                 yv = View(C.c_void_p(big.data_ptr()), n, h4, w4, 0, ktot, 0, ktot)
-                self._conv(dt, B['hid'].view(), yv, self._w_heads2(dt), b2, 1, 1, 0,
+                self._conv(dt, B['hid'].view(), yv, self._fetch(P, ('heads2', 'f'))[0], b2, 1, 1, 0,
                            512 * nh, 64, _lib.EPI_BIAS | _lib.EPI_F32_NCHW, alg_ci=512)
             o = 0
             for stem, k in heads:
                 if big is not None:
                     outs[stem] = big[:, o:o + k].contiguous()
                 o += k
-        lin_rf = os.environ.get('DBX_REFINE_LINEAR', '1') != '0'     # training: the branch by its linear structure (0: the three convs; A/B, tests)
         P.refine_fwd = None
-        if kind != 'DenseBox' and (not train or lin_rf):
+        rf_convs = ('conv6_1_det', 'f') in P.manifest    # training under DBX_REFINE_LINEAR=0: the three convs (A/B, tests), else by its linear structure
+        if kind != 'DenseBox' and not rf_convs:
             # refine branch (DenseBox.py:464-471): nothing after the pooling is non-linear, the 1x1 conv commutes with the up-sampling
             # -> cat + pool + ONE un-padded 7x7 conv 5 -> 1 in a single fp32 kernel on the heads' fp32 outputs, then the up-sampling of
             # that one map (was: two layout kernels, pool, three convs, a 64-channel up-sampling: 60 us of a 0.46-ms image).  Training
@@ -922,24 +870,21 @@ class Engine:
                 P.refine_fwd = (lmk, det, wf7, vf7)  # the backward pass re-derives everything else from these (dbx_refine_backward)
         elif kind != 'DenseBox':
             # refine branch: cat(landmarks, score) -> pool4 -> 3x3 -> 5x5 -> bilinear -> 1x1   (DenseBox.py:464-471)
-            rdt = P.rdt
-            saved, self._defer = self._defer, None            # (fp32 refine weights: packed on their own, cached on the parameter versions)
-            w61, w62, w63 = (self._w_fwd(rdt, 'conv6_1_det', P.crf, 64), self._w_fwd(rdt, 'conv6_2_det', 64, 64),
-                             self._w_fwd(rdt, 'conv6_3_det', 64, 64))
-            self._defer = saved
+            rdt = P.rdt                 # (weights of another element type than the plan's are outside the pack table: _fetch)
+            w61, w62, w63 = (self._fetch(P, (st, 'f'))[0] for st in ('conv6_1_det', 'conv6_2_det', 'conv6_3_det'))
             rin = B['rf_in'].view()
             check(L.dbx_nchw_to_framed_ch(rdt, ptr(outs['landmark']), 4, C.byref(rin), 0, s))
             check(L.dbx_nchw_to_framed_ch(rdt, ptr(outs['det']), 1, C.byref(rin), 4, s))
             check(L.dbx_maxpool2x2(rdt, C.byref(rin), C.byref(B['rf_p'].view()), s))
             self._conv(rdt, B['rf_p'].view(), B['rf_1'].view(), w61,
-                       self._bias(['conv6_1_det'], 64), 3, 3, 0, P.crf, 64, _lib.EPI_BIAS, alg_ci=5)
+                       self._fetch(P, ('conv6_1_det', 'bias'))[0], 3, 3, 0, P.crf, 64, _lib.EPI_BIAS, alg_ci=5)
             self._conv(rdt, B['rf_1'].view(), B['rf_2'].view(), w62,
-                       self._bias(['conv6_2_det'], 64), 5, 5, 0, 64, 64, _lib.EPI_BIAS)
+                       self._fetch(P, ('conv6_2_det', 'bias'))[0], 5, 5, 0, 64, 64, _lib.EPI_BIAS)
             check(L.dbx_upsample_bilinear(rdt, C.byref(B['rf_2'].view()), C.byref(B['rf_u'].view()), s))
             o = torch.empty((n, 1, h4, w4), dtype=torch.float32, device=dev)
             yv = View(C.c_void_p(o.data_ptr()), n, h4, w4, 0, 1, 0, 1)
             self._conv(rdt, B['rf_u'].view(), yv, w63,
-                       self._bias(['conv6_3_det'], 64), 1, 1, 0, 64, 64, _lib.EPI_BIAS | _lib.EPI_F32_NCHW)
+                       self._fetch(P, ('conv6_3_det', 'bias'))[0], 1, 1, 0, 64, 64, _lib.EPI_BIAS | _lib.EPI_F32_NCHW)
             outs['refine'] = o
         return outs
 
@@ -972,39 +917,6 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ backward
-    def _w_bwd(self, dt, stem, rows_pad, cin_pad, frag=False):
-        """dgrad weights: rows = input channels, K = [flipped tap][output channel]."""
-        w = self._param(stem + '.weight')
-        mode = 5 if frag else 1
-        return self._packed((stem, mode, dt),
-                            lambda old: self._pack(dt, mode, w, rows_pad, cin_pad, w.shape[2], w.shape[3], out=old),
-                            (w._version, w.data_ptr()))
-
-    def _w_heads1_bwd(self, dt, frag=False):
-        heads = _HEADS[self.kind]
-        ws = [self._param('conv5_1_%s.weight' % s) for s, _ in heads]
-        mode = 5 if frag else 1
-
-        def build(out):
-            for i, w in enumerate(ws):
-                out = self._pack(dt, mode, w, 768, 512 * len(ws), 1, 1, out=out, k_off=512 * i)
-            return out
-        return self._packed(('heads1', mode, dt), build, tuple((w._version, w.data_ptr()) for w in ws))
-
-    def _w_heads1_bwd_part(self, dt, part, frag=False):
-        """dgrad weights of one part of the fusion concat: rows = that part's input channels (part 'a': 0..511, the up-sampled
-        conv4_4; 'c': 512..767, conv3_4), K = the 512 nh hidden channels of all heads."""
-        heads = _HEADS[self.kind]
-        ws = [self._param('conv5_1_%s.weight' % s) for s, _ in heads]
-        mode = 5 if frag else 1
-        rows, roff = (512, 0) if part == 'a' else (256, -512)
-
-        def build(out):
-            for i, w in enumerate(ws):
-                out = self._pack(dt, mode, w, rows, 512 * len(ws), 1, 1, out=out, row_off=roff, k_off=512 * i)
-            return out
-        return self._packed(('heads1_' + part, mode, dt), build, tuple((w._version, w.data_ptr()) for w in ws))
-
     def _lin_bwd(self, dt):
         """Heads backward by linearity of the bilinear up-sampling (16-bit types): W [up(a44); c34] = up(W_a a44) + W_c c34, so the
         conv4_4 part of the 768 -> 512 nh GEMM's data and weight gradients runs on conv4_4's 30x30 grid (a quarter of the pixels)
@@ -1028,34 +940,31 @@ class Engine:
         need = self.L.dbx_conv_wgrad_scratch_bytes(dt, C.byref(dz), C.byref(x), kh, kw)
         if getattr(self, '_wg_scratch', None) is None or self._wg_scratch.numel() < need:
             self._wg_scratch = torch.empty(int(need * 1.25) + 1024, dtype=torch.uint8, device=dw.device)
-        prof = self.profile
-        if prof is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        if pool is not None:
-            dyv, nib, nch, write_dz = pool
-            check(self.L.dbx_conv_wgrad_pool_dz(dt, C.byref(dyv), ptr(nib), nch, C.byref(dz), C.byref(x), kh, kw, cpad, co, ci, ptr(dw), ptr(db),
-                                                ptr(self._wg_scratch), accumulate, write_dz, stream_ptr()))
-        elif gen is not None:
-            dov, w2p, ks, nh, use_hash, seed = gen
-            check(self.L.dbx_heads1_wgrad_gen(dt, C.byref(dov), C.byref(x), w2p, ks, nh, use_hash, seed, ci, ptr(dw), ci_total, ci_off, ptr(db),
-                                              ptr(self._wg_scratch), stream_ptr()))
-        elif ci_total is None:
-            check(self.L.dbx_conv_wgrad(dt, C.byref(dz), C.byref(x), kh, kw, cpad, co, ci, ptr(dw), ptr(db),
-                                        ptr(self._wg_scratch), accumulate, stream_ptr()))
-        else:
-            check(self.L.dbx_conv_wgrad_slice(dt, C.byref(dz), C.byref(x), kh, kw, cpad, co, ci, ptr(dw), ci_total, ci_off, ptr(db),
-                                              ptr(self._wg_scratch), accumulate, stream_ptr()))
-        if prof is not None:
-            ev1.record()
+
+        def name():
             buf = C.create_string_buffer(64)                      # the library's own choice (dbx_conv_wgrad_plan)
             check(self.L.dbx_conv_wgrad_plan(dt, C.byref(dz), C.byref(x), kh, kw, buf, 64, None))
-            name = buf.value.decode()
+            nm = buf.value.decode()
             if gen is not None:
-                name = name.replace('>', ',gen>')
+                nm = nm.replace('>', ',gen>')
             if pool is not None:
-                name = name.replace('>', ',pool+dz>' if pool[3] else ',pool>')
-            prof.append({'kernel': name, 'flops': 2.0 * dz.n * dz.h * dz.w * kh * kw * ci * co, 'start': ev0, 'end': ev1})
+                nm = nm.replace('>', ',pool+dz>' if pool[3] else ',pool>')
+            return nm
+        with self._timed(name, 2.0 * dz.n * dz.h * dz.w * kh * kw * ci * co):
+            if pool is not None:
+                dyv, nib, nch, write_dz = pool
+                check(self.L.dbx_conv_wgrad_pool_dz(dt, C.byref(dyv), ptr(nib), nch, C.byref(dz), C.byref(x), kh, kw, cpad, co, ci, ptr(dw), ptr(db),
+                                                    ptr(self._wg_scratch), accumulate, write_dz, stream_ptr()))
+            elif gen is not None:
+                dov, w2p, ks, nh, use_hash, seed = gen
+                check(self.L.dbx_heads1_wgrad_gen(dt, C.byref(dov), C.byref(x), w2p, ks, nh, use_hash, seed, ci, ptr(dw), ci_total, ci_off, ptr(db),
+                                                  ptr(self._wg_scratch), stream_ptr()))
+            elif ci_total is None:
+                check(self.L.dbx_conv_wgrad(dt, C.byref(dz), C.byref(x), kh, kw, cpad, co, ci, ptr(dw), ptr(db),
+                                            ptr(self._wg_scratch), accumulate, stream_ptr()))
+            else:
+                check(self.L.dbx_conv_wgrad_slice(dt, C.byref(dz), C.byref(x), kh, kw, cpad, co, ci, ptr(dw), ci_total, ci_off, ptr(db),
+                                                  ptr(self._wg_scratch), accumulate, stream_ptr()))
 
     def backward_raw(self, grad_outs):
         """grad_outs: dict output-name -> fp32 NCHW tensor (or None).  Returns dict param-name -> fp32 gradient.
@@ -1064,6 +973,7 @@ class Engine:
         P = self.last_plan
         assert P is not None and P.train, 'backward needs a preceding training-mode forward'
         B, dt, n = P.B, P.dtype_id, P.n
+        M = self._manifest(P)
         s = stream_ptr()
         dev = P.ws.device
         heads = _HEADS[kind]
@@ -1124,9 +1034,8 @@ class Engine:
             on_side(run)
 
         def dgrad(stem, src, dst, kh, kw, cpad, rows_pad, cin_pad, gate=None, epi=0, dropmask=None):
-            frag = stem in _BWD_IO and kh == 3 and self._frag(P, dt, stem, 'b')
-            wp = self._w_bwd(dt, stem, rows_pad, cin_pad, frag=frag)
-            e = epi | (_lib.EPI_GATE if gate is not None else 0) | (_lib.CONV_WFRAG if frag else 0)
+            wp, wfrag = self._fetch(P, (stem, 'b'))
+            e = epi | (_lib.EPI_GATE if gate is not None else 0) | wfrag
             self._conv(dt, src, dst, wp, None, kh, kw, cpad, cin_pad, rows_pad, e, gate=gate, dropmask=dropmask,
                        dm_ld=512 * nh)
 
@@ -1155,7 +1064,7 @@ class Engine:
                 sink.ready(pn)
             override = {'landmark': o_lm, 'det': o_det}
             # (P.refine_fwd stays: the forward pass resets it, and a second backward over the same forward -- retain_graph -- re-runs this path)
-        elif kind != 'DenseBox' and os.environ.get('DBX_REFINE_LINEAR', '1') != '0':
+        elif kind != 'DenseBox' and ('conv6_1_det', 'b') not in M:
             raise RuntimeError('densebox_amd: backward of the refine branch without its forward state (no training-mode forward on this plan)')
         elif kind != 'DenseBox':
             d_rfo = B['d_rfo'].view()
@@ -1195,16 +1104,12 @@ class Engine:
             self._h2_scratch = torch.empty(int(need), dtype=torch.uint8, device=dev)
         dw2 = [new_grad('conv5_2_%s.weight' % st) for st, _ in heads]
         db2 = [new_grad('conv5_2_%s.bias' % st) for st, _ in heads]
-        prof = self.profile
-        if prof is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
         w2s = [self._param('conv5_2_%s.weight' % st).detach() for st, _ in heads]      # fp32 [k,512,1,1]
         ks = (C.c_int32 * nh)(*[k for _, k in heads])
         h2_names = ['conv5_2_%s.weight' % st for st, _ in heads] + ['conv5_2_%s.bias' % st for st, _ in heads]
         mask_p = C.c_void_p(P.mask_buf.data_ptr()) if (P.drop_active and not P.drop_hash) else None
         hash_on, hash_seed = (1 if P.drop_hash else 0), (P.drop_seed if P.drop_hash else 0)
-        lin = self._lin_bwd(dt)
+        lin = ('heads1', 'bwd_a') in M          # backward by linearity of the up-sampling (_lin_bwd, asked when the manifest was built)
         up_done = False
         # the hidden gradient d_hid = keep * (d_out W2): generated inside its two 60x60 consumers (no 944 MB map written and read twice) when
         # the plan holds no buffer for it and nothing needs it in memory (an injected dropout mask, the side-stream schedule do)
@@ -1214,38 +1119,36 @@ class Engine:
         else:
             dhid_v = self._d_hid(P).view()
         w2p = (C.c_void_p * nh)(*[w.data_ptr() for w in w2s])
-        if side is not None:
-            def run_h2():
-                check(L.dbx_head2_wgrad(dt, C.byref(B['d_out'].view()), C.byref(hv), ks, nh,
-                                        (C.c_void_p * nh)(*[t.data_ptr() for t in dw2]), (C.c_void_p * nh)(*[t.data_ptr() for t in db2]),
-                                        ptr(self._h2_scratch), stream_ptr()))
+        with self._timed(lambda: ('head2_backward_up_kernel<%s>' if up_done else 'head2_wgrad_kernel<%s>') % _TNAME[dt],
+                         2.0 * hv.n * hv.h * hv.w * 512 * sum(k for _, k in heads) * (1 if side is not None else 2)):
+            if side is not None:
+                def run_h2():
+                    check(L.dbx_head2_wgrad(dt, C.byref(B['d_out'].view()), C.byref(hv), ks, nh,
+                                            (C.c_void_p * nh)(*[t.data_ptr() for t in dw2]), (C.c_void_p * nh)(*[t.data_ptr() for t in db2]),
+                                            ptr(self._h2_scratch), stream_ptr()))
+                    if sink is not None:
+                        sink.ready(h2_names)
+                on_side(run_h2)
+                check(L.dbx_head2_dgrad(dt, C.byref(B['d_out'].view()), (C.c_void_p * nh)(*[w.data_ptr() for w in w2s]), ks, nh,
+                                        C.byref(dhid_v), mask_p, 512 * nh, hash_on, hash_seed, s))
+            elif lin:   # one pass over the pixels, and the hidden gradient goes to conv4_4's grid (d_g44 = up^T(d_hid)) while it is in registers
+                check(L.dbx_head2_backward_up(dt, C.byref(B['d_out'].view()), C.byref(hv), (C.c_void_p * nh)(*[w.data_ptr() for w in w2s]), ks, nh,
+                                              C.byref(dhid_v), mask_p, 512 * nh, hash_on, hash_seed,
+                                              (C.c_void_p * nh)(*[t.data_ptr() for t in dw2]), (C.c_void_p * nh)(*[t.data_ptr() for t in db2]),
+                                              ptr(self._h2_scratch), C.byref(B['d_g44'].view()), s))
+                up_done = True
+                if gen and dt == _lib.F32:
+                    # fp32 parity runs of the generating structure: d_hid had to be written (no fp32 form of the call leaves it out); nothing behind
+                    # this point may read it -- a consumer that did would return NaN gradients
+                    bh = P.B['d_hid']
+                    P.ws[bh.off:bh.off + bh.bytes].view(torch.float32).fill_(float('nan'))
+            else:       # one pass over the pixels: the d_hid write overlaps the hid read
+                check(L.dbx_head2_backward(dt, C.byref(B['d_out'].view()), C.byref(hv), (C.c_void_p * nh)(*[w.data_ptr() for w in w2s]), ks, nh,
+                                           C.byref(dhid_v), mask_p, 512 * nh, hash_on, hash_seed,
+                                           (C.c_void_p * nh)(*[t.data_ptr() for t in dw2]), (C.c_void_p * nh)(*[t.data_ptr() for t in db2]),
+                                           ptr(self._h2_scratch), s))
                 if sink is not None:
                     sink.ready(h2_names)
-            on_side(run_h2)
-            check(L.dbx_head2_dgrad(dt, C.byref(B['d_out'].view()), (C.c_void_p * nh)(*[w.data_ptr() for w in w2s]), ks, nh,
-                                    C.byref(dhid_v), mask_p, 512 * nh, hash_on, hash_seed, s))
-        elif lin:   # one pass over the pixels, and the hidden gradient goes to conv4_4's grid (d_g44 = up^T(d_hid)) while it is in registers
-            check(L.dbx_head2_backward_up(dt, C.byref(B['d_out'].view()), C.byref(hv), (C.c_void_p * nh)(*[w.data_ptr() for w in w2s]), ks, nh,
-                                          C.byref(dhid_v), mask_p, 512 * nh, hash_on, hash_seed,
-                                          (C.c_void_p * nh)(*[t.data_ptr() for t in dw2]), (C.c_void_p * nh)(*[t.data_ptr() for t in db2]),
-                                          ptr(self._h2_scratch), C.byref(B['d_g44'].view()), s))
-            up_done = True
-            if gen and dt == _lib.F32:
-                # fp32 parity runs of the generating structure: d_hid had to be written (no fp32 form of the call leaves it out); nothing behind
-                # this point may read it -- a consumer that did would return NaN gradients
-                bh = P.B['d_hid']
-                P.ws[bh.off:bh.off + bh.bytes].view(torch.float32).fill_(float('nan'))
-        else:       # one pass over the pixels: the d_hid write overlaps the hid read
-            check(L.dbx_head2_backward(dt, C.byref(B['d_out'].view()), C.byref(hv), (C.c_void_p * nh)(*[w.data_ptr() for w in w2s]), ks, nh,
-                                       C.byref(dhid_v), mask_p, 512 * nh, hash_on, hash_seed,
-                                       (C.c_void_p * nh)(*[t.data_ptr() for t in dw2]), (C.c_void_p * nh)(*[t.data_ptr() for t in db2]),
-                                       ptr(self._h2_scratch), s))
-            if sink is not None:
-                sink.ready(h2_names)
-        if prof is not None:
-            ev1.record()
-            prof.append({'kernel': ('head2_backward_up_kernel<%s>' if up_done else 'head2_wgrad_kernel<%s>') % ('f16', 'bf16', 'f32')[dt],
-                         'flops': 2.0 * hv.n * hv.h * hv.w * 512 * sum(k for _, k in heads) * (1 if side is not None else 2), 'start': ev0, 'end': ev1})
         w1n = ['conv5_1_%s.weight' % st for st, _ in heads]
         b1n = ['conv5_1_%s.bias' % st for st, _ in heads]
         if sink is not None:           # the heads' conv5_1 gradients are adjacent in the flat buffer (grad_order)
@@ -1274,52 +1177,37 @@ class Engine:
         for i, (stem, _) in enumerate(heads):
             G['conv5_1_%s.weight' % stem] = dw1[512 * i:512 * (i + 1)]
             G['conv5_1_%s.bias' % stem] = db1[512 * i:512 * (i + 1)]
-        row_bytes = 512 * nh * _lib.ESIZE[dt]
         if lin:
             # data gradients of the two concat parts: d_a44 = gate(W_a^T d_g44) at 30x30, d_c34 = gate(W_c^T d_hid) at 60x60
-            fa, fc = self._frag_heads(P, dt, 'ba'), self._frag_heads(P, dt, 'bc')
-            self._conv(dt, B['d_g44'].view(), B['d_a44'].view(), self._w_heads1_bwd_part(dt, 'a', frag=fa), None, 1, 1, 0, 512 * nh, 512,
-                       _lib.EPI_GATE | (_lib.CONV_WFRAG if fa else 0), gate=B['a44'].view())
-            if gen:
-                if prof is not None:
-                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    ev0.record()
-                check(L.dbx_heads1_dgrad_gen(dt, C.byref(B['d_out'].view()), w2p, ks, nh, hash_on, hash_seed,
-                                             ptr(self._w_heads1_bwd_part(dt, 'c', frag=dt != _lib.F32)), C.byref(B['d_c34'].view()), C.byref(c34), s))
-                if prof is not None:
-                    ev1.record()
-                    prof.append({'kernel': 'heads1_dgrad_gen_kernel<%s>' % ('f16', 'bf16', 'f32')[dt],
-                                 'flops': 2.0 * hv.n * hv.h * hv.w * 512 * nh * (256 + 8), 'start': ev0, 'end': ev1})
+            wa, fa = self._fetch(P, ('heads1', 'bwd_a'))
+            self._conv(dt, B['d_g44'].view(), B['d_a44'].view(), wa, None, 1, 1, 0, 512 * nh, 512, _lib.EPI_GATE | fa, gate=B['a44'].view())
+            if gen:       # (a generating plan's manifest holds the image dbx_heads1_dgrad_gen reads: fragment order, plain for its fp32 form)
+                wc = self._fetch(P, ('heads1', 'bwd_c'))[0]
+                with self._timed('heads1_dgrad_gen_kernel<%s>' % _TNAME[dt], 2.0 * hv.n * hv.h * hv.w * 512 * nh * (256 + 8)):
+                    check(L.dbx_heads1_dgrad_gen(dt, C.byref(B['d_out'].view()), w2p, ks, nh, hash_on, hash_seed,
+                                                 ptr(wc), C.byref(B['d_c34'].view()), C.byref(c34), s))
             else:
-                if fc and getattr(P, 'heads_gen', False):      # (the plan chose the fragment image for the generating kernel: does this GEMM take it?)
-                    fc = self.conv_plan(dt, dhid_v, B['d_c34'].view(), 1, 1, 0, 512 * nh, 256, _lib.EPI_GATE)[2]
-                self._conv(dt, dhid_v, B['d_c34'].view(), self._w_heads1_bwd_part(dt, 'c', frag=fc), None, 1, 1, 0, 512 * nh, 256,
-                           _lib.EPI_GATE | (_lib.CONV_WFRAG if fc else 0), gate=c34)
-        elif dt != _lib.F32:
-            bfrag = self._frag_heads(P, dt, 'b')
-            w1t = self._w_heads1_bwd(dt, frag=bfrag)              # [768 rows][512*nh] (or its fragment-order image)
-            # one pass over d_hid for both branches of the concat: couts 0..511 -> d_ups, 512..767 -> d_c34 (ReLU-gated)
-            d = ConvDesc(dt, 1, 1, 0, 512 * nh, 768, _lib.CONV_WFRAG if bfrag else 0, 0)
-            prof = self.profile
-            if prof is not None:
-                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ev0.record()
-            check(L.dbx_conv_forward_split(C.byref(d), C.byref(dhid_v), ptr(w1t), None, C.byref(B['d_ups'].view()), None,
-                                           C.byref(B['d_c34'].view()), C.byref(c34), 512, _lib.EPI_GATE, s))
-            if prof is not None:
-                ev1.record()
-                hv = dhid_v
+                # (... and this GEMM over the on-demand d_hid takes that image only if the library runs it on the ws kernel)
+                plain = P.heads_gen and M[('heads1', 'bwd_c')].mode >= 4 and \
+                    not self.conv_plan(dt, dhid_v, B['d_c34'].view(), 1, 1, 0, 512 * nh, 256, _lib.EPI_GATE)[2]
+                wc, fc = self._fetch(P, ('heads1', 'bwd_c'), plain=plain)
+                self._conv(dt, dhid_v, B['d_c34'].view(), wc, None, 1, 1, 0, 512 * nh, 256, _lib.EPI_GATE | fc, gate=c34)
+        else:
+            w1t, bfrag = self._fetch(P, ('heads1', 'bwd'))          # [768 rows][512*nh] (or its fragment-order image; fp32: plain)
+            if dt != _lib.F32:
+                # one pass over d_hid for both branches of the concat: couts 0..511 -> d_ups, 512..767 -> d_c34 (ReLU-gated)
+                d = ConvDesc(dt, 1, 1, 0, 512 * nh, 768, bfrag, 0)
                 dv = B['d_ups'].view()
                 both = View(dv.ptr, dv.n, dv.h, dv.w, dv.pad, 768, 0, 768)
-                prof.append({'kernel': self.conv_plan(dt, hv, both, 1, 1, 0, 512 * nh, 768, 0)[1] if bfrag else
-                             'conv_igemm_dma_kernel<%s,256,256>' % ('f16', 'bf16', 'f32')[dt],
-                             'flops': 2.0 * hv.n * hv.h * hv.w * 512 * nh * 768, 'start': ev0, 'end': ev1})
-        else:
-            w1t = self._w_heads1_bwd(dt, frag=False)
-            self._conv(dt, dhid_v, B['d_ups'].view(), w1t, None, 1, 1, 0, 512 * nh, 512, 0)
-            self._conv(dt, dhid_v, B['d_c34'].view(), w1t[512 * row_bytes:], None, 1, 1, 0, 512 * nh, 256,
-                       _lib.EPI_GATE, gate=c34)
-        if not lin:
+                with self._timed((lambda: self.conv_plan(dt, dhid_v, both, 1, 1, 0, 512 * nh, 768, 0)[1]) if bfrag else
+                                 'conv_igemm_dma_kernel<%s,256,256>' % _TNAME[dt], 2.0 * hv.n * hv.h * hv.w * 512 * nh * 768):
+                    check(L.dbx_conv_forward_split(C.byref(d), C.byref(dhid_v), ptr(w1t), None, C.byref(B['d_ups'].view()), None,
+                                                   C.byref(B['d_c34'].view()), C.byref(c34), 512, _lib.EPI_GATE, s))
+            else:
+                row_bytes = 512 * nh * _lib.ESIZE[dt]
+                self._conv(dt, dhid_v, B['d_ups'].view(), w1t, None, 1, 1, 0, 512 * nh, 512, 0)
+                self._conv(dt, dhid_v, B['d_c34'].view(), w1t[512 * row_bytes:], None, 1, 1, 0, 512 * nh, 256,
+                           _lib.EPI_GATE, gate=c34)
             check(L.dbx_upsample_bilinear_bwd(dt, C.byref(B['d_ups'].view()), C.byref(B['d_a44'].view()),
                                               C.byref(B['a44'].view()), s))
 
@@ -1362,15 +1250,11 @@ class Engine:
                     if getattr(self, '_wg1_scratch', None) is None or self._wg1_scratch.numel() < need:
                         self._wg1_scratch = torch.empty(int(need), dtype=torch.uint8, device=dev)
                     dw1, db1 = new_grad('conv1_1_1.weight'), new_grad('conv1_1_1.bias')
-                    if prof is not None:
-                        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        ev0.record()
-                    check(L.dbx_conv_dgrad_wgrad1(C.byref(d12), C.byref(dzv), ptr(self._w_bwd(dt, stem, 64, 64, frag=False)),
-                                                  C.byref(gv), C.byref(x0v), 3, ptr(dw1), ptr(db1), ptr(self._wg1_scratch), 0, s))
-                    if prof is not None:
-                        ev1.record()
-                        prof.append({'kernel': self.conv_plan(dt, dzv, B[dxn].view(), 3, 3, 1, 64, 64, _lib.EPI_GATE)[1],
-                                     'flops': 2.0 * dzv.n * dzv.h * dzv.w * 9 * 64 * (64 + 3), 'start': ev0, 'end': ev1})
+                    w12 = self._fetch(P, (stem, 'b'), plain=True)[0]        # (this kernel reads plain-order weights)
+                    with self._timed(lambda: self.conv_plan(dt, dzv, B[dxn].view(), 3, 3, 1, 64, 64, _lib.EPI_GATE)[1],
+                                     2.0 * dzv.n * dzv.h * dzv.w * 9 * 64 * (64 + 3)):
+                        check(L.dbx_conv_dgrad_wgrad1(C.byref(d12), C.byref(dzv), ptr(w12), C.byref(gv), C.byref(x0v), 3, ptr(dw1), ptr(db1),
+                                                      ptr(self._wg1_scratch), 0, s))
                     if sink is not None:
                         sink.ready(['conv1_1_1.weight', 'conv1_1_1.bias'])
                     fused11 = True
