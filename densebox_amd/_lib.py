@@ -106,6 +106,11 @@ class OverlayStyle(C.Structure):
                 ('radius', C.c_int32), ('font_scale', C.c_int32), ('inset_scale', C.c_int32)]
 
 
+class RedactStyle(C.Structure):
+    _fields_ = [('color', C.c_uint8 * 4), ('method', C.c_int32), ('shape', C.c_int32), ('cell', C.c_int32), ('radius', C.c_int32),
+                ('grow', C.c_int32), ('grow_pct', C.c_int32), ('coast', C.c_int32), ('min_score', C.c_double)]
+
+
 class ResizeJob(C.Structure):
     _fields_ = [('src', C.c_void_p), ('sh', C.c_int32), ('sw', C.c_int32), ('cx0', C.c_int32), ('cy0', C.c_int32),
                 ('cw', C.c_int32), ('ch', C.c_int32), ('pad_l', C.c_int32), ('pad_t', C.c_int32), ('pad_r', C.c_int32),
@@ -229,6 +234,9 @@ SIGNATURES = {
                                          C.POINTER(OverlayStyle), _VP]),
     'dbx_overlay_font': (C.c_int, [_VP]),
     'dbx_overlay_label': (C.c_int, [_D, _I32, C.c_char_p, _I32]),
+    'dbx_redact_batch': (C.c_int, [_VP, _I32, _I32, _I32, _I32, _VP, _I32, _I64, _VP, _VP, _I32, _VP, _I32, _I32, _I32,
+                                   C.POINTER(RedactStyle), _VP]),
+    'dbx_redact_host': (C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP, _I32, _I32, _VP, _I32, _VP, _I32, C.POINTER(RedactStyle)]),
     'dbx_resize_batch_workspace_bytes': (_I64, [_I32]),
     'dbx_resize_cubic_batch_u8': (C.c_int, [C.POINTER(ResizeJob), _I32, _I32, _VP, _VP, _VP]),
     'dbx_patch_plan': (C.c_int, [C.POINTER(PatchPlanIO), _I32, _I32, _I32, _I32, _I32, _D, _D, _I32, _VP]),

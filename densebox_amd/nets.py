@@ -181,6 +181,15 @@ class _DenseBoxBase(nn.Module):
         return annotate_batch(self, frames, tracker=tracker, stream0=stream0, inset=inset, K=K, nms_thresh=nms_thresh,
                               max_batch=max_batch, style=style)
 
+    def redact_batch(self, frames, *, tracker=None, stream0=0, K=10, nms_thresh=0.4, max_batch=32, style=None):
+        """detect_batch() (track_batch() with a tracker) on uint8 frames, then every kept row's plate and -- with a tracker -- every
+        coasting track's predicted box filled, pixelated or blurred on the device (style: a redact.Redaction), in eval mode in one
+        hipGraph per chunk: a list of (dets, keep, track_id or None, redacted [H,W,3]) in input order
+        (densebox_amd.redact.net_redact_batch)."""
+        from .redact import net_redact_batch
+        return net_redact_batch(self, frames, tracker=tracker, stream0=stream0, K=K, nms_thresh=nms_thresh, max_batch=max_batch,
+                                style=style)
+
     def detect_batch_resized(self, images, size=720, K=10, nms_thresh=0.4, max_batch=32, score_thresh=None, max_dets=1024):
         """detect_batch() on uint8 frames of any sizes, each padded to a square and resized to size x size in one launch; a list of
         (dets, keep) in input order, coordinates mapped back to the source frames (densebox_amd.decode.detect_batch_resized)."""

@@ -74,7 +74,9 @@ const char* dbx_last_error(void);
  *      also at 13, without a bump: dbx_upsample_bwd_plan_t, dbx_upsample_bilinear_bwd_plan (which kernel dbx_upsample_bilinear_bwd
  *      launches: a read-only host query), a pure addition likewise
  *      also at 13, without a bump: dbx_patch_warp_rec, dbx_patch_warp_cfg, dbx_patch_warp_io, dbx_patch_warp_plan, dbx_patch_warp,
- *      dbx_patch_warp_params_host, dbx_patch_warp_host (training patches warped on the device), pure additions likewise */
+ *      dbx_patch_warp_params_host, dbx_patch_warp_host (training patches warped on the device), pure additions likewise
+ *      also at 13, without a bump: dbx_redact_style, dbx_redact_batch, dbx_redact_host (plates made unreadable on the device), pure
+ *      additions likewise */
 #define DBX_ABI_VERSION 13
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
@@ -911,6 +913,83 @@ int dbx_draw_overlay_batch(const dbx_overlay_frame* frames, int32_t batch, int32
                            const dbx_overlay_style* style, void* stream);
 int dbx_overlay_font(uint8_t* out);
 int dbx_overlay_label(double score, int32_t track_id, char* out, int32_t out_len);
+
+/* ---- plate redaction (no reference counterpart): the frame with every plate made unreadable, written on the device behind the decode
+ * and the tracking update.  The semantics are this project's own, restated in NumPy by tests/redact_ref.py ----
+ * dbx_redact_batch: ONE launch, a workgroup of 256 threads per 64 x 16 tile of a frame on a grid of (the tiles of a max_h x max_w frame,
+ * batch); it copies nothing from the host and never synchronises, so it can be captured into a hipGraph behind the decode and
+ * dbx_track_update_batch.
+ * frames: a DEVICE table of `batch` dbx_overlay_frame records, as for dbx_draw_overlay_batch: frame b is an interleaved uint8 [h][w][c]
+ * image, read at src and written at dst.  dets / det_cols / det_rows / keep / prefix / slots: the decoded-rows description every such
+ * entry point takes (prefix == NULL: slot layout; otherwise dbx_detect_thresh_batch's packed layout), slots in 1..1024.  tracks:
+ * const dbx_track [streams][max_tracks] as dbx_track_update_batch left it, or NULL (streams, stream0 and max_tracks are then not read);
+ * frame b belongs to stream stream0 + b.
+ * Notation: I(v), T(v) and "usable" as for dbx_draw_overlay_batch.  All arithmetic is integer.
+ * Regions of frame b:
+ *   1  every kept row (the keep count clamped, a keep entry outside the frame's rows ignored, as everywhere else).  A row is skipped only
+ *      when row[4] < min_score, so a NaN score is redacted.  A row whose x1, y1, x2, y2 are not all usable has no region.
+ *   2  when tracks is given and coast > 0: every slot of the stream with id >= 0, 1 <= age <= coast and a usable box -- the coasting
+ *      tracks, whose box is the prediction for a frame in which the detector missed the plate.  Always a box region.
+ * Box region: L, R, Tp, Bt as in the overlay; gx = grow + ((R - L + 1) * grow_pct) / 100 and gy likewise on Bt - Tp + 1, in int64; the
+ * region is L-gx <= x <= R+gx, Tp-gy <= y <= Bt+gy, clipped to the frame.
+ * Quad region (shape == 1 and det_cols == 13): P_q = (I(row[5+2q]), I(row[6+2q])), q = 0..3.  The row falls back to its box region
+ * when a landmark is not finite or has |v| >= 2^20, or when the shoelace sum of P_0..P_3 (the sum over q of Px_q Py_q+1 - Px_q+1 Py_q,
+ * indices mod 4) is 0.  Otherwise, in quarter pixels and per axis: S = P_0 + P_1 + P_2 + P_3, d = 4 P_q - S,
+ * G_q = 4 P_q + (d * grow_pct) / 100 + 4 * grow * sgn(d) (C's division, truncating toward zero), and the region is
+ * tri(G_0, G_1, G_2) u tri(G_0, G_2, G_3) clipped to the frame: the pixel (x, y) is inside a triangle when its three int64 edge
+ * functions at (4x, 4y), (b - a) x (p - a) for the edges a->b = G_i->G_j, G_j->G_k, G_k->G_i, multiplied by the sign of the triangle's
+ * doubled area, are all >= 0; a triangle of zero area covers nothing.
+ * Value: a pixel no region covers keeps src.  A covered pixel's value depends on src alone, so neither list order nor scheduling matters:
+ *   fill      (method 0) dst[ch] = color[ch].
+ *   pixelate  (method 1) cells of s = cell pixels anchored to the frame's origin: the cell of (x, y) is [s*(x/s), min(s*(x/s)+s, w)) x
+ *             [s*(y/s), min(s*(y/s)+s, h)), of n pixels; dst[ch] = (sum of src[ch] over the cell + n/2) / n.  Pixels of the cell
+ *             outside every region count in the sum.
+ *   blur      (method 2) r = radius, A = (2r+1)^2: dst[ch] = (sum over dy, dx in [-r, r] of src[clamp(y+dy, 0, h-1)][clamp(x+dx, 0,
+ *             w-1)][ch] + A/2) / A.  The 2-D sum is exact: nothing is rounded between the horizontal and the vertical pass.
+ * dst == src is allowed for fill only; a record with dst == src under pixelate or blur is skipped (other workgroups read src outside
+ * their tile), as is, with its dst not written, a record with a null src or dst, a non-positive size, h > max_h or w > max_w.  A frame
+ * with a bad prefix pair has no rows; it is still copied and its coasting tracks still apply.  For every frame not skipped the call
+ * writes every byte of dst (in place: every byte that changes) and nothing outside it.  A tile no region meets is moved with 16-byte
+ * accesses where src and dst allow the same ones, bytes at the ragged ends.  Device data is never trusted as a bound: age, id and the
+ * box values of tracks are data, not indices.
+ * Kernel shape: a tile is 64 x 16 pixels, four per thread.  Per tile the workgroup collects in LDS the regions whose bounding rectangle
+ * (clipped to the frame) meets the tile -- the kept rows, then the stream's track slots, 256 candidates at a time, compacted by a
+ * ballot prefix -- at 52 bytes per region (rectangle, the four G_q, kind), room for slots + max_tracks of them (max_tracks only with
+ * tracks and coast > 0).  A tile with regions then stages, for pixelate, the rounded mean of every cell that meets the tile (4 bytes
+ * per cell, at most ((63 / s) + 2) * ((15 / s) + 2) cells; each cell summed from src by a group of min(64, s*s rounded up to a power of
+ * two) lanes, so a cell that straddles a tile seam is summed once by each tile it meets), and for blur the tile with its halo of r
+ * pixels, clamped to the frame, (64 + 2r) * (16 + 2r) * c bytes, and its horizontal window sums as uint16, (16 + 2r) * 64 * c * 2 bytes:
+ * 18432 + 24576 bytes at r = 16, c = 4.  At the limits (1024 + 256 regions, blur, r = 16, c = 4) that is 66560 + 43008 = 109568
+ * bytes of the CU's 160 KiB; with 10 rows and 64 track slots, 3848 bytes of list.  There is no scratch buffer and there are no atomics.
+ * Refused with DBX_ERR_ARG before anything is queued: batch < 0, c outside 1..4, max_h or max_w < 1, det_cols not 5 or 13, slots
+ * outside 1..1024, det_rows < 0 (or below batch * slots in slot layout), method outside 0..2, shape outside 0..1, cell outside 2..32,
+ * radius outside 1..16, grow outside 0..64, grow_pct outside 0..100, coast < 0, a NaN min_score, tracks given with stream0 < 0,
+ * stream0 + batch > streams or max_tracks outside 1..256, a null frames / dets / keep / style, more than 2^24 - 1 tiles or 65535 frames
+ * (one grid).  batch == 0: no-op.
+ * dbx_redact_style is 40 bytes (color 0, method 4, shape 8, cell 12, radius 16, grow 20, grow_pct 24, coast 28, min_score 32).
+ *
+ * dbx_redact_host: the same region build, coverage test and value rules compiled for the host (no GPU needed), applied to ONE frame:
+ * src and dst are host images [h][w][c]; rows float64 [n][det_cols] and keep, k row numbers of which the first min(k, n) are walked
+ * (the device's clamp with slots = n); tracks, ntracks dbx_track records, or NULL.  It refuses what dbx_redact_batch refuses as far as
+ * it applies, and also h or w < 1, n or k < 0, a null src or dst, null rows with n > 0, null keep with k > 0, ntracks outside 1..256
+ * with tracks given, and dst == src under pixelate or blur. */
+typedef struct dbx_redact_style {
+    uint8_t color[4];      /* fill: channel ch of a covered pixel takes color[ch] */
+    int32_t method;        /* 0 fill, 1 pixelate, 2 blur */
+    int32_t shape;         /* 0 box, 1 quad (rows of 13 columns; others fall back to the box) */
+    int32_t cell;          /* 2..32, pixelate's cell side */
+    int32_t radius;        /* 1..16, blur's window is (2 radius + 1)^2 */
+    int32_t grow;          /* 0..64 pixels added on every side */
+    int32_t grow_pct;      /* 0..100 per cent of the region's size added on every side */
+    int32_t coast;         /* >= 0: tracks of age 1..coast are redacted; 0: none */
+    double  min_score;     /* rows with row[4] below it are skipped */
+} dbx_redact_style;
+int dbx_redact_batch(const dbx_overlay_frame* frames, int32_t batch, int32_t c, int32_t max_h, int32_t max_w, const double* dets,
+                     int32_t det_cols, int64_t det_rows, const int32_t* keep, const int32_t* prefix, int32_t slots,
+                     const dbx_track* tracks, int32_t streams, int32_t stream0, int32_t max_tracks, const dbx_redact_style* style,
+                     void* stream);
+int dbx_redact_host(const uint8_t* src, uint8_t* dst, int32_t h, int32_t w, int32_t c, const double* rows, int32_t det_cols, int32_t n,
+                    const int32_t* keep, int32_t k, const dbx_track* tracks, int32_t ntracks, const dbx_redact_style* style);
 
 /* ---- batched pad + bicubic resize (pad_img + cv2.resize(..., INTER_CUBIC), DenseBox.py:1282-1340; the patch cutters' resize of a
  * cropped window) ----
