@@ -1,8 +1,9 @@
 // The description of a batch of decoded rows as the decodes leave them on the device -- dets, det_cols, det_rows, keep, prefix, batch,
 // slots, in the slot layout of dbx_detect_batch (prefix == NULL) or the packed layout of dbx_detect_thresh_batch -- shared by every
 // entry point that takes it and every kernel that walks the kept rows: eval_ops.hip (dbx_match_gt_batch, dbx_eval_append),
-// track_ops.hip (dbx_track_update_batch) and viz_ops.hip (dbx_draw_overlay_batch).  Integer arithmetic only, and it has to stay so:
-// eval_ops.hip and track_ops.hip compile with `#pragma clang fp contract(off)`, viz_ops.hip without, which makes no difference here.
+// track_ops.hip (dbx_track_update_batch), viz_ops.hip (dbx_draw_overlay_batch) and redact_ops.hip (dbx_redact_batch).  Integer
+// arithmetic only, and it has to stay so: eval_ops.hip and track_ops.hip compile with `#pragma clang fp contract(off)`, viz_ops.hip and
+// redact_ops.hip without, which makes no difference here.
 #pragma once
 #include "common.hpp"
 

@@ -7,8 +7,8 @@
 
 #include "common.hpp"
 #include "det_frame.hpp"
+#include "frame_tile.hpp"
 
-#define RED_THREADS 256
 #define RED_TW 64                    // a tile: 64 x 16 pixels, 4 per thread; the copy moves a row segment with 16 lanes
 #define RED_TH 16
 #define RED_MAX_SLOTS 1024
@@ -24,21 +24,18 @@ static_assert(sizeof(dbx_redact_style) == 40 && offsetof(dbx_redact_style, metho
 // (never empty); g: the quad's G_0..G_3 in quarter pixels (x, y interleaved); quad: 1 when g counts.
 struct RedEnt { int x0, x1, y0, y1; int g[8]; int quad; };
 
-__host__ __device__ static inline bool red_usable(double v) { return fabs(v) < 1073741824.0; }    // false for NaN and the infinities
-__host__ __device__ static inline bool red_landmark(double v) { return fabs(v) < 1048576.0; }     // likewise, |v| < 2^20
-template <typename T> __host__ __device__ static inline T red_min(T a, T b) { return b < a ? b : a; }
-template <typename T> __host__ __device__ static inline T red_max(T a, T b) { return b > a ? b : a; }
+__host__ __device__ static inline bool red_landmark(double v) { return fabs(v) < 1048576.0; }     // |v| < 2^20: false for NaN and the infinities
 __host__ __device__ static inline long long red_sgn(long long v) { return v > 0 ? 1 : (v < 0 ? -1 : 0); }
 
 // The box region of (x1, y1, x2, y2) = bx[0..3] on an h x w frame; false when a value is not usable or nothing of it is in the frame.
 __host__ __device__ static inline bool red_box(const double* bx, const dbx_redact_style& st, int h, int w, RedEnt& e) {
     const double v0 = bx[0], v1 = bx[1], v2 = bx[2], v3 = bx[3];
-    if (!(red_usable(v0) && red_usable(v1) && red_usable(v2) && red_usable(v3))) return false;
+    if (!(tile_usable(v0) && tile_usable(v1) && tile_usable(v2) && tile_usable(v3))) return false;
     const long long X1 = (int)(v0 + 0.5), Y1 = (int)(v1 + 0.5), X2 = (int)(v2 + 0.5), Y2 = (int)(v3 + 0.5);
-    const long long L = red_min(X1, X2), R = red_max(X1, X2), Tp = red_min(Y1, Y2), Bt = red_max(Y1, Y2);
+    const long long L = tile_min(X1, X2), R = tile_max(X1, X2), Tp = tile_min(Y1, Y2), Bt = tile_max(Y1, Y2);
     const long long gx = st.grow + ((R - L + 1) * st.grow_pct) / 100, gy = st.grow + ((Bt - Tp + 1) * st.grow_pct) / 100;
-    const long long xa = red_max(L - gx, 0ll), xb = red_min(R + gx, (long long)w - 1);
-    const long long ya = red_max(Tp - gy, 0ll), yb = red_min(Bt + gy, (long long)h - 1);
+    const long long xa = tile_max(L - gx, 0ll), xb = tile_min(R + gx, (long long)w - 1);
+    const long long ya = tile_max(Tp - gy, 0ll), yb = tile_min(Bt + gy, (long long)h - 1);
     if (xa > xb || ya > yb) return false;
     e.x0 = (int)xa; e.x1 = (int)xb; e.y0 = (int)ya; e.y1 = (int)yb;
 #pragma unroll
@@ -69,12 +66,12 @@ __host__ __device__ static inline int red_quad(const double* lm, const dbx_redac
         const long long gx = 4 * px[q] + (dx * st.grow_pct) / 100 + 4 * st.grow * red_sgn(dx);
         const long long gy = 4 * py[q] + (dy * st.grow_pct) / 100 + 4 * st.grow * red_sgn(dy);
         e.g[2 * q] = (int)gx; e.g[2 * q + 1] = (int)gy;                 // |G| < 2^24
-        xlo = q ? red_min(xlo, gx) : gx; xhi = q ? red_max(xhi, gx) : gx;
-        ylo = q ? red_min(ylo, gy) : gy; yhi = q ? red_max(yhi, gy) : gy;
+        xlo = q ? tile_min(xlo, gx) : gx; xhi = q ? tile_max(xhi, gx) : gx;
+        ylo = q ? tile_min(ylo, gy) : gy; yhi = q ? tile_max(yhi, gy) : gy;
     }
     // a covered pixel has xlo <= 4x <= xhi: floor(xlo / 4) <= x <= floor(xhi / 4)
-    const long long xa = red_max(xlo >> 2, 0ll), xb = red_min(xhi >> 2, (long long)w - 1);
-    const long long ya = red_max(ylo >> 2, 0ll), yb = red_min(yhi >> 2, (long long)h - 1);
+    const long long xa = tile_max(xlo >> 2, 0ll), xb = tile_min(xhi >> 2, (long long)w - 1);
+    const long long ya = tile_max(ylo >> 2, 0ll), yb = tile_min(yhi >> 2, (long long)h - 1);
     if (xa > xb || ya > yb) return -1;
     e.x0 = (int)xa; e.x1 = (int)xb; e.y0 = (int)ya; e.y1 = (int)yb;
     e.quad = 1;
@@ -84,7 +81,7 @@ __host__ __device__ static inline int red_quad(const double* lm, const dbx_redac
 // The region of a decoded row d of det_cols columns; false when it has none in the frame.
 __host__ __device__ static inline bool red_row_region(const double* d, int det_cols, const dbx_redact_style& st, int h, int w, RedEnt& e) {
     if (d[4] < st.min_score) return false;                             // (a NaN score is redacted)
-    if (!(red_usable(d[0]) && red_usable(d[1]) && red_usable(d[2]) && red_usable(d[3]))) return false;
+    if (!(tile_usable(d[0]) && tile_usable(d[1]) && tile_usable(d[2]) && tile_usable(d[3]))) return false;
     if (st.shape == 1 && det_cols == 13) {
         const int q = red_quad(d + 5, st, h, w, e);
         if (q) return q > 0;
@@ -124,7 +121,7 @@ __host__ __device__ static inline int red_clamp(int v, int lo, int hi) { return 
 // the cell [a, b) of coordinate v on an axis of `lim` pixels
 __host__ __device__ static inline void red_cell(int s, int v, int lim, int& a, int& b) {
     a = s * (v / s);
-    b = (int)red_min((long long)a + s, (long long)lim);
+    b = (int)tile_min((long long)a + s, (long long)lim);
 }
 
 // pixelate and blur straight from the image (the kernel stages the same sums in LDS)
@@ -164,80 +161,37 @@ struct RedArgs {
     unsigned list_bytes;
 };
 
-// n bytes from src to dst by lanes q of nq, as viz_ops.hip moves them: 16-byte words where both addresses allow the same ones, else
-// dwords, else bytes; the bytes in front of the first whole word and behind the last one go as bytes.
-__device__ static inline void red_copy(uint8_t* dst, const uint8_t* src, size_t n, int q, int nq) {
-    const uintptr_t d = (uintptr_t)dst, s = (uintptr_t)src;
-    const size_t word = ((d ^ s) & 15) == 0 ? 16 : (((d ^ s) & 3) == 0 ? 4 : 1);
-    size_t head = (word - (d & (word - 1))) & (word - 1);
-    if (head > n) head = n;
-    const size_t body = (n - head) / word;
-    for (size_t i = q; i < head; i += nq) dst[i] = src[i];
-    if (word == 16) {
-        u32x4* dw = (u32x4*)(dst + head);
-        const u32x4* sw = (const u32x4*)(src + head);
-        for (size_t i = q; i < body; i += nq) dw[i] = sw[i];
-    } else if (word == 4) {
-        unsigned* dw = (unsigned*)(dst + head);
-        const unsigned* sw = (const unsigned*)(src + head);
-        for (size_t i = q; i < body; i += nq) dw[i] = sw[i];
-    }
-    for (size_t i = head + (word > 1 ? body * word : 0) + q; i < n; i += nq) dst[i] = src[i];
-}
-
-// One workgroup per 64 x 16 tile of a frame (grid: the tiles of a max_h x max_w frame, batch).  The workgroup collects in LDS the
-// regions that meet the tile: the kept rows, then the stream's track slots, 256 candidates at a time, compacted by a ballot prefix
-// (the order does not matter: the regions are a union).  A tile that none meets -- most of them -- is copied row segment by row
-// segment.  Otherwise the tile's cell means (pixelate) or its halo and horizontal window sums (blur) are staged in LDS from src, and
-// every pixel takes its value when a region covers it and src's otherwise.
-__global__ __launch_bounds__(RED_THREADS) void redact_batch_kernel(const RedArgs a) {
+// One workgroup per 64 x 16 tile of a frame (grid: the tiles of a max_h x max_w frame, batch), walked as frame_tile.hpp says.  The
+// candidates are the frame's kept rows, then the stream's track slots, and their regions are a union: the list's order does not
+// matter.  For a tile that some region meets, the tile's cell means (pixelate) or its halo and horizontal window sums (blur) are staged
+// in LDS from src, and every pixel takes its value when a region covers it and src's otherwise.
+__global__ __launch_bounds__(TILE_THREADS) void redact_batch_kernel(const RedArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char red_sm[];
-    __shared__ int wsum[RED_THREADS / 64];
     RedEnt* list = (RedEnt*)red_sm;
     unsigned char* work = red_sm + a.list_bytes;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
-    const dbx_overlay_frame fm = a.frames[b];
-    if (!fm.src || !fm.dst || fm.h < 1 || fm.w < 1 || fm.h > a.max_h || fm.w > a.max_w) return;        // uniform, as every return below
-    const int method = a.st.method;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y, c = a.c, method = a.st.method;
+    FrameTile t;
+    if (!tile_open<RED_TW, RED_TH>(a.frames, a.tiles_x, a.max_h, a.max_w, t)) return;              // uniform, as every return below
+    const dbx_overlay_frame fm = t.fm;
     if (method != 0 && fm.dst == fm.src) return;
-    const int x0 = (int)(blockIdx.x % a.tiles_x) * RED_TW, y0 = (int)(blockIdx.x / a.tiles_x) * RED_TH;
-    if (x0 >= fm.w || y0 >= fm.h) return;
-    const int c = a.c, rows = min(RED_TH, fm.h - y0), cols = min(RED_TW, fm.w - x0);
+    const int x0 = t.x0, y0 = t.y0, rows = t.rows, cols = t.cols;
 
     const DetFrame fr = det_frame(a.keep, a.prefix, b, a.slots, a.det_rows);
     const bool coasting = a.tracks && a.st.coast > 0;
     const dbx_track* tr = coasting ? a.tracks + (size_t)(a.stream0 + b) * a.max_tracks : nullptr;
     const int total = fr.k + (coasting ? a.max_tracks : 0);            // at most slots + max_tracks = cap
-    int cnt = 0;
-    for (int c0 = 0; c0 < total; c0 += RED_THREADS) {
-        const int i = c0 + tid;
+    const int cnt = tile_collect(list, total, [&](int i, RedEnt& e) {
         bool hit = false;
-        RedEnt e;
         if (i < fr.k) {
             const int r = fr.kl[1 + i];
             if (r >= 0 && r < fr.n) hit = red_row_region(a.dets + (size_t)(fr.r0 + r) * a.det_cols, a.det_cols, a.st, fm.h, fm.w, e);
-        } else if (i < total) {
+        } else {
             hit = red_track_region(tr + (i - fr.k), a.st, fm.h, fm.w, e);
         }
-        if (hit) hit = e.x0 < x0 + cols && e.x1 >= x0 && e.y0 < y0 + rows && e.y1 >= y0;
-        const unsigned long long m = __ballot(hit);
-        if (lane == 0) wsum[wave] = __popcll(m);
-        __syncthreads();
-        int off = 0, sum = 0;
-#pragma unroll
-        for (int w = 0; w < RED_THREADS / 64; ++w) { off += w < wave ? wsum[w] : 0; sum += wsum[w]; }
-        if (hit) list[cnt + off + __popcll(m & ((1ull << lane) - 1ull))] = e;
-        cnt += sum;
-        __syncthreads();                                           // wsum is rewritten by the next chunk; the list is read below
-    }
-
-    const bool copying = fm.dst != fm.src;
-    if (cnt == 0) {                                                // uniform
-        const size_t nb = (size_t)cols * c;
-        for (int rr = tid >> 4; copying && rr < rows; rr += RED_THREADS / 16) {
-            const size_t o = ((size_t)(y0 + rr) * fm.w + x0) * c;
-            red_copy(fm.dst + o, fm.src + o, nb, tid & 15, 16);
-        }
+        return hit && tile_meets(t, e.x0, e.x1, e.y0, e.y1);
+    });
+    if (cnt == 0) {
+        tile_copy_through<RED_TW>(t, c);
         return;
     }
 
@@ -251,7 +205,7 @@ __global__ __launch_bounds__(RED_THREADS) void redact_batch_kernel(const RedArgs
         int G = 1;                                                 // lanes per cell
         while (G < s * s && G < 64) G <<= 1;
         const int per_wave = 64 / G, sub = lane & (G - 1), ncell = ncx * ncy;
-        for (int base = wave * per_wave; base < ncell; base += (RED_THREADS / 64) * per_wave) {     // uniform within a wave
+        for (int base = wave * per_wave; base < ncell; base += (TILE_THREADS / 64) * per_wave) {     // uniform within a wave
             const int cell = base + lane / G;
             int s0 = 0, s1 = 0, s2 = 0, s3 = 0, n = 1;
             if (cell < ncell) {
@@ -279,13 +233,13 @@ __global__ __launch_bounds__(RED_THREADS) void redact_batch_kernel(const RedArgs
     } else if (method == 2) {
         uint8_t* hal = work;
         unsigned short* hs = (unsigned short*)(work + red_halo_bytes(r, c));
-        for (int i = tid; i < hw * hh; i += RED_THREADS) {
+        for (int i = tid; i < hw * hh; i += TILE_THREADS) {
             const int ly = i / hw, lx = i - ly * hw;
             const uint8_t* q = fm.src + ((size_t)red_clamp(y0 + ly - r, 0, fm.h - 1) * fm.w + red_clamp(x0 + lx - r, 0, fm.w - 1)) * c;
             for (int ch = 0; ch < c; ++ch) hal[(size_t)i * c + ch] = q[ch];
         }
         __syncthreads();
-        for (int i = tid; i < hh * cols * c; i += RED_THREADS) {
+        for (int i = tid; i < hh * cols * c; i += TILE_THREADS) {
             const int ch = i % c, lx = (i / c) % cols, ly = i / (c * cols);
             const uint8_t* q = hal + ((size_t)ly * hw + lx) * c + ch;
             int sum = 0;
@@ -295,10 +249,13 @@ __global__ __launch_bounds__(RED_THREADS) void redact_batch_kernel(const RedArgs
         __syncthreads();
     }
 
+    // The pixels, by a loop of the kernel's own: as a shared skeleton over a lambda the same inner loops came out in another block
+    // order, and blur, whose covered pixels cost most, measured 0.8 % slower (profiles/r21_frame_tile.txt).
     unsigned col;                                                  // color[ch] in byte ch
     __builtin_memcpy(&col, a.st.color, 4);
     const int area = (2 * r + 1) * (2 * r + 1);
-    for (int p = tid; p < RED_TW * RED_TH; p += RED_THREADS) {
+    const bool copying = fm.dst != fm.src;
+    for (int p = tid; p < RED_TW * RED_TH; p += TILE_THREADS) {
         const int lx = p & (RED_TW - 1), ly = p / RED_TW;
         if (lx >= cols || ly >= rows) continue;
         const int x = x0 + lx, y = y0 + ly;
@@ -323,8 +280,7 @@ __global__ __launch_bounds__(RED_THREADS) void redact_batch_kernel(const RedArgs
 }
 
 // ---------------------------------------------------------------------------------------------------------------- entry points
-static int red_style_check(const char* fn, int32_t c, const dbx_redact_style* st) {
-    DBX_REQUIRE(c >= 1 && c <= 4, "%s: c=%d must be 1..4", fn, c);
+static int red_style_check(const char* fn, const dbx_redact_style* st) {
     DBX_REQUIRE(st, "%s: null style", fn);
     DBX_REQUIRE(st->method >= 0 && st->method <= 2, "%s: method=%d must be 0 (fill), 1 (pixelate) or 2 (blur)", fn, st->method);
     DBX_REQUIRE(st->shape >= 0 && st->shape <= 1, "%s: shape=%d must be 0 (box) or 1 (quad)", fn, st->shape);
@@ -345,9 +301,8 @@ extern "C" int dbx_redact_batch(const dbx_overlay_frame* frames, int32_t batch, 
     static_assert(sizeof(RedEnt) == 52, "a collected region is 52 bytes of LDS");
     const char* fn = "redact_batch";
     int rc = det_rows_check(fn, det_cols, det_rows, prefix, batch, slots, RED_MAX_SLOTS);
-    if (rc != DBX_OK) return rc;
-    DBX_REQUIRE(max_h >= 1 && max_w >= 1, "%s: max_h=%d and max_w=%d must be positive", fn, max_h, max_w);
-    rc = red_style_check(fn, c, style);
+    if (rc == DBX_OK) rc = tile_dims_check(fn, c, max_h, max_w);
+    if (rc == DBX_OK) rc = red_style_check(fn, style);
     if (rc != DBX_OK) return rc;
     if (tracks) {
         DBX_REQUIRE(stream0 >= 0 && (int64_t)stream0 + batch <= streams, "%s: streams %d..%lld do not fit the %d of the table", fn, stream0,
@@ -355,29 +310,21 @@ extern "C" int dbx_redact_batch(const dbx_overlay_frame* frames, int32_t batch, 
         DBX_REQUIRE(max_tracks >= 1 && max_tracks <= RED_MAX_TRACKS, "%s: max_tracks=%d must be 1..%d", fn, max_tracks, RED_MAX_TRACKS);
     }
     DBX_REQUIRE(frames && dets && keep, "%s: null argument", fn);
-    const int64_t tiles_x = ((int64_t)max_w + RED_TW - 1) / RED_TW, tiles_y = ((int64_t)max_h + RED_TH - 1) / RED_TH;
-    DBX_REQUIRE(tiles_x * tiles_y < (1 << 24) && batch <= 65535, "%s: %lld tiles x %d frames exceed one grid (2^24 - 1 tiles, 65535 frames)", fn,
-                (long long)(tiles_x * tiles_y), batch);
-    if (batch == 0) return DBX_OK;
+    RedArgs a;
+    dim3 grid;
+    rc = tile_grid<RED_TW, RED_TH>(fn, max_h, max_w, batch, &grid, &a.tiles_x);
+    if (rc != DBX_OK || batch == 0) return rc;
     const bool coasting = tracks && style->coast > 0;
     const int cap = slots + (coasting ? max_tracks : 0);
     const size_t lds = red_list_bytes(cap) + red_work_bytes(*style, c);
-    if (lds > 32768) {
-        static DbxDevOnce attr_once; int attr_dev = 0;
-        if (attr_once.pending(&attr_dev)) {
-            dbx_redact_style worst = *style;
-            worst.method = 2; worst.radius = RED_MAX_RADIUS;
-            DBX_HIP(hipFuncSetAttribute((const void*)redact_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)(red_list_bytes(RED_MAX_SLOTS + RED_MAX_TRACKS) + red_work_bytes(worst, 4))));
-            attr_once.mark(attr_dev);
-        }
-    }
-    RedArgs a;
+    dbx_redact_style worst = *style;
+    worst.method = 2; worst.radius = RED_MAX_RADIUS;
+    rc = tile_lds_limit<redact_batch_kernel>(lds, red_list_bytes(RED_MAX_SLOTS + RED_MAX_TRACKS) + red_work_bytes(worst, 4));
+    if (rc != DBX_OK) return rc;
     a.frames = frames; a.dets = dets; a.keep = keep; a.prefix = prefix; a.tracks = coasting ? tracks : nullptr;
     a.det_rows = det_rows; a.st = *style; a.c = c; a.det_cols = det_cols; a.slots = slots; a.stream0 = stream0; a.max_tracks = max_tracks;
-    a.cap = cap; a.max_h = max_h; a.max_w = max_w; a.tiles_x = (int)tiles_x; a.list_bytes = (unsigned)red_list_bytes(cap);
-    hipLaunchKernelGGL(redact_batch_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)batch), dim3(RED_THREADS), lds,
-                       (hipStream_t)stream, a);
+    a.cap = cap; a.max_h = max_h; a.max_w = max_w; a.list_bytes = (unsigned)red_list_bytes(cap);
+    hipLaunchKernelGGL(redact_batch_kernel, grid, dim3(TILE_THREADS), lds, (hipStream_t)stream, a);
     DBX_LAUNCH_CHECK();
     return DBX_OK;
 }
@@ -389,7 +336,8 @@ extern "C" int dbx_redact_host(const uint8_t* src, uint8_t* dst, int32_t h, int3
     DBX_REQUIRE(det_cols == 5 || det_cols == 13, "%s: det_cols=%d must be 5 or 13", fn, det_cols);
     DBX_REQUIRE(h >= 1 && w >= 1, "%s: a frame of %d x %d pixels is empty", fn, w, h);
     DBX_REQUIRE(n >= 0 && k >= 0, "%s: n=%d and k=%d must not be negative", fn, n, k);
-    const int rc = red_style_check(fn, c, style);
+    DBX_REQUIRE(c >= 1 && c <= 4, "%s: c=%d must be 1..4", fn, c);
+    const int rc = red_style_check(fn, style);
     if (rc != DBX_OK) return rc;
     DBX_REQUIRE(!tracks || (ntracks >= 1 && ntracks <= RED_MAX_TRACKS), "%s: ntracks=%d must be 1..%d", fn, ntracks, RED_MAX_TRACKS);
     DBX_REQUIRE(src && dst && (rows || n == 0) && (keep || k == 0), "%s: null argument", fn);
@@ -397,7 +345,7 @@ extern "C" int dbx_redact_host(const uint8_t* src, uint8_t* dst, int32_t h, int3
     const dbx_redact_style st = *style;
     std::vector<RedEnt> list;
     RedEnt e;
-    for (int i = 0; i < red_min(k, n); ++i) {
+    for (int i = 0; i < tile_min(k, n); ++i) {
         const int r = keep[i];
         if (r >= 0 && r < n && red_row_region(rows + (size_t)r * det_cols, det_cols, st, h, w, e)) list.push_back(e);
     }

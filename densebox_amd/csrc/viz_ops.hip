@@ -6,8 +6,8 @@
 // alone: integer arithmetic behind one float64 add per coordinate.
 #include "common.hpp"
 #include "det_frame.hpp"
+#include "frame_tile.hpp"
 
-#define VIZ_THREADS 256
 #define VIZ_TW 128                   // a tile: 128 x 16 pixels, 8 per thread; the copy moves a row segment with 32 lanes
 #define VIZ_TH 16
 #define VIZ_MAX_SLOTS 1024
@@ -101,46 +101,42 @@ struct VizArgs {
 struct VizEnt { unsigned long long tlo, thi; int x1, y1, x2, y2; int cx[4], cy[4]; int word, pad; int bx0, bx1, by0, by1; };
 static size_t viz_lds_bytes(int slots) { return ((size_t)slots * sizeof(VizEnt) + 15) & ~(size_t)15; }
 
-__host__ __device__ static inline bool viz_usable(double v) { return fabs(v) < 1073741824.0; }   // false for NaN and the infinities
-template <typename T> __host__ __device__ static inline T viz_min(T a, T b) { return b < a ? b : a; }
-template <typename T> __host__ __device__ static inline T viz_max(T a, T b) { return b > a ? b : a; }
-
 // Row d at list position i of frame b as entry e, and the bounding rectangle box = (x min, x max, y min, y max) of everything it
 // paints (with the longest label; viz_entry_label makes the text); false when the row paints nothing.
 __host__ __device__ static inline bool viz_entry(const VizArgs& a, int b, int i, const double* d, VizEnt& e, long long* box) {
     const double bx1 = d[0], by1 = d[1], bx2 = d[2], by2 = d[3];
-    if (!(viz_usable(bx1) && viz_usable(by1) && viz_usable(bx2) && viz_usable(by2))) return false;
+    if (!(tile_usable(bx1) && tile_usable(by1) && tile_usable(bx2) && tile_usable(by2))) return false;
     const int ta = a.st.thickness / 2, s = a.st.font_scale, rad = a.st.radius;
     e.x1 = (int)(bx1 + 0.5); e.y1 = (int)(by1 + 0.5); e.x2 = (int)(bx2 + 0.5); e.y2 = (int)(by2 + 0.5);
-    const int L = viz_min(e.x1, e.x2), R = viz_max(e.x1, e.x2), Tp = viz_min(e.y1, e.y2), Bt = viz_max(e.y1, e.y2);
+    const int L = tile_min(e.x1, e.x2), R = tile_max(e.x1, e.x2), Tp = tile_min(e.y1, e.y2), Bt = tile_max(e.y1, e.y2);
     long long xa = L - ta, xb = R + ta, ya = Tp - ta, yb = Bt + ta;
     int word = i;
     e.tlo = e.thi = 0ull; e.pad = 0;
     if (s > 0) {                                                   // (the longest label: the text is made by viz_entry_label, for the rows a tile keeps)
-        xa = viz_min(xa, (long long)e.x1); xb = viz_max(xb, (long long)e.x1 + 6 * s * VIZ_MAX_LABEL + 3);
-        ya = viz_min(ya, (long long)e.y1 - 8 * s - 5); yb = viz_max(yb, (long long)e.y1);
+        xa = tile_min(xa, (long long)e.x1); xb = tile_max(xb, (long long)e.x1 + 6 * s * VIZ_MAX_LABEL + 3);
+        ya = tile_min(ya, (long long)e.y1 - 8 * s - 5); yb = tile_max(yb, (long long)e.y1);
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         e.cx[q] = e.cy[q] = 0;
         if (a.det_cols != 13 || rad < 0) continue;
         const double px = d[5 + 2 * q], py = d[6 + 2 * q];
-        if (!viz_usable(px) || !viz_usable(py)) continue;
+        if (!tile_usable(px) || !tile_usable(py)) continue;
         e.cx[q] = (int)px; e.cy[q] = (int)py;
         word |= 1 << (15 + q);
-        xa = viz_min(xa, (long long)e.cx[q] - rad); xb = viz_max(xb, (long long)e.cx[q] + rad);
-        ya = viz_min(ya, (long long)e.cy[q] - rad); yb = viz_max(yb, (long long)e.cy[q] + rad);
+        xa = tile_min(xa, (long long)e.cx[q] - rad); xb = tile_max(xb, (long long)e.cx[q] + rad);
+        ya = tile_min(ya, (long long)e.cy[q] - rad); yb = tile_max(yb, (long long)e.cy[q] + rad);
     }
     if (a.crops && a.ok[(size_t)b * a.slots + i] != 0) {
         word |= 1 << 19;
         const long long px = L - ta, py = (long long)Bt + ta + 2;
-        xa = viz_min(xa, px); xb = viz_max(xb, px + (long long)a.ow * a.st.inset_scale - 1);
-        ya = viz_min(ya, py); yb = viz_max(yb, py + (long long)a.oh * a.st.inset_scale - 1);
+        xa = tile_min(xa, px); xb = tile_max(xb, px + (long long)a.ow * a.st.inset_scale - 1);
+        ya = tile_min(ya, py); yb = tile_max(yb, py + (long long)a.oh * a.st.inset_scale - 1);
     }
     e.word = word;
     box[0] = xa; box[1] = xb; box[2] = ya; box[3] = yb;
     const long long lo = -2147483647ll - 1, hi = 2147483647ll;
-    e.bx0 = (int)viz_max(xa, lo); e.bx1 = (int)viz_min(xb, hi); e.by0 = (int)viz_max(ya, lo); e.by1 = (int)viz_min(yb, hi);
+    e.bx0 = (int)tile_max(xa, lo); e.bx1 = (int)tile_min(xb, hi); e.by0 = (int)tile_max(ya, lo); e.by1 = (int)tile_min(yb, hi);
     return true;
 }
 
@@ -153,33 +149,12 @@ __host__ __device__ static inline void viz_entry_label(const VizArgs& a, int b, 
     e.word |= lab.n << 10;
 }
 
-// n bytes from src to dst by lanes q of nq: 16-byte words where both addresses allow the same ones, else dwords, else bytes; the bytes in
-// front of the first whole word and behind the last one go as bytes.
-__device__ static inline void viz_copy(uint8_t* dst, const uint8_t* src, size_t n, int q, int nq) {
-    const uintptr_t d = (uintptr_t)dst, s = (uintptr_t)src;
-    const size_t word = ((d ^ s) & 15) == 0 ? 16 : (((d ^ s) & 3) == 0 ? 4 : 1);
-    size_t head = (word - (d & (word - 1))) & (word - 1);
-    if (head > n) head = n;
-    const size_t body = (n - head) / word;
-    for (size_t i = q; i < head; i += nq) dst[i] = src[i];
-    if (word == 16) {
-        u32x4* dw = (u32x4*)(dst + head);
-        const u32x4* sw = (const u32x4*)(src + head);
-        for (size_t i = q; i < body; i += nq) dw[i] = sw[i];
-    } else if (word == 4) {
-        unsigned* dw = (unsigned*)(dst + head);
-        const unsigned* sw = (const unsigned*)(src + head);
-        for (size_t i = q; i < body; i += nq) dw[i] = sw[i];
-    }
-    for (size_t i = head + (word > 1 ? body * word : 0) + q; i < n; i += nq) dst[i] = src[i];
-}
-
 // What row e paints at (x, y), its primitives tried from the last painted to the first: 0 nothing, 1 box colour, 2 text colour, 3 mark
 // colour, 4 the crop pixel *cp.
 __host__ __device__ static inline int viz_hit(const VizEnt& e, const VizArgs& a, int b, int x, int y, const uint8_t** cp) {
     if (x < e.bx0 || x > e.bx1 || y < e.by0 || y > e.by1) return 0;
     const int t = a.st.thickness, ta = t / 2, tb = t - ta, s = a.st.font_scale, w = e.word;
-    const int L = viz_min(e.x1, e.x2), R = viz_max(e.x1, e.x2), Tp = viz_min(e.y1, e.y2), Bt = viz_max(e.y1, e.y2);
+    const int L = tile_min(e.x1, e.x2), R = tile_max(e.x1, e.x2), Tp = tile_min(e.y1, e.y2), Bt = tile_max(e.y1, e.y2);
     if (w & (1 << 19)) {
         const long long m = a.st.inset_scale, dx = (long long)x - (L - ta), dy = (long long)y - (Bt + ta + 2);
         if (dx >= 0 && dy >= 0 && dx < a.ow * m && dy < a.oh * m) {
@@ -209,62 +184,40 @@ __host__ __device__ static inline int viz_hit(const VizEnt& e, const VizArgs& a,
     return 0;
 }
 
-// One workgroup per 128 x 16 tile of a frame (grid: the tiles of a max_h x max_w frame, batch).  The workgroup collects in LDS, in list
-// order, the kept rows whose primitives' bounding rectangle meets the tile (a ballot prefix per chunk of 256 list positions); a tile
-// that none meets -- most of them -- is copied, row segment by row segment, and one that some meet is resolved pixel by pixel: the list
-// walked from the back to the first row that paints the pixel, the source's pixel where none does.
-__global__ __launch_bounds__(VIZ_THREADS) void draw_overlay_batch_kernel(const VizArgs a) {
+// One workgroup per 128 x 16 tile of a frame (grid: the tiles of a max_h x max_w frame, batch), walked as frame_tile.hpp says.  The
+// candidates are the frame's kept rows, and a row meets the tile when the bounding rectangle of its primitives does; the list keeps
+// list order.  A pixel is resolved by walking the list from the back to the first row that paints it.
+__global__ __launch_bounds__(TILE_THREADS) void draw_overlay_batch_kernel(const VizArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char viz_sm[];
-    __shared__ int wsum[VIZ_THREADS / 64];
     VizEnt* list = (VizEnt*)viz_sm;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
-    const dbx_overlay_frame fm = a.frames[b];
-    if (!fm.src || !fm.dst || fm.h < 1 || fm.w < 1 || fm.h > a.max_h || fm.w > a.max_w) return;        // uniform, as every return below
-    const int x0 = (int)(blockIdx.x % a.tiles_x) * VIZ_TW, y0 = (int)(blockIdx.x / a.tiles_x) * VIZ_TH;
-    if (x0 >= fm.w || y0 >= fm.h) return;
-    const int c = a.c, rows = min(VIZ_TH, fm.h - y0), cols = min(VIZ_TW, fm.w - x0);
+    const int b = blockIdx.y, c = a.c;
+    FrameTile t;
+    if (!tile_open<VIZ_TW, VIZ_TH>(a.frames, a.tiles_x, a.max_h, a.max_w, t)) return;              // uniform, as the return below
     unsigned cbox, ctext, cmark;                                   // colour[ch] in byte ch
     __builtin_memcpy(&cbox, a.st.box_color, 4); __builtin_memcpy(&ctext, a.st.text_color, 4); __builtin_memcpy(&cmark, a.st.mark_color, 4);
 
     const DetFrame fr = det_frame(a.keep, a.prefix, b, a.slots, a.det_rows);
-    int cnt = 0;
-    for (int c0 = 0; c0 < fr.k; c0 += VIZ_THREADS) {
-        const int i = c0 + tid;
-        bool hit = false;
-        VizEnt e;
-        if (i < fr.k) {
-            const int r = fr.kl[1 + i];
-            if (r >= 0 && r < fr.n) {
-                const double* d = a.dets + (size_t)(fr.r0 + r) * a.det_cols;
-                long long box[4];
-                if (viz_entry(a, b, i, d, e, box)) hit = box[0] < (long long)x0 + cols && box[1] >= x0 && box[2] < (long long)y0 + rows && box[3] >= y0;
-                if (hit) viz_entry_label(a, b, i, d, e);
-            }
-        }
-        const unsigned long long m = __ballot(hit);
-        if (lane == 0) wsum[wave] = __popcll(m);
-        __syncthreads();
-        int off = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < VIZ_THREADS / 64; ++w) { off += w < wave ? wsum[w] : 0; total += wsum[w]; }
-        if (hit) list[cnt + off + __popcll(m & ((1ull << lane) - 1ull))] = e;
-        cnt += total;
-        __syncthreads();                                           // wsum is rewritten by the next chunk; the list is read below
-    }
-
-    const bool copying = fm.dst != fm.src;
-    if (cnt == 0) {                                                // uniform
-        const size_t nb = (size_t)cols * c;
-        for (int rr = tid >> 5; copying && rr < rows; rr += VIZ_THREADS / 32) {
-            const size_t o = ((size_t)(y0 + rr) * fm.w + x0) * c;
-            viz_copy(fm.dst + o, fm.src + o, nb, tid & 31, 32);
-        }
+    const int cnt = tile_collect(list, fr.k, [&](int i, VizEnt& e) {
+        const int r = fr.kl[1 + i];
+        if (r < 0 || r >= fr.n) return false;
+        const double* d = a.dets + (size_t)(fr.r0 + r) * a.det_cols;
+        long long box[4];
+        if (!viz_entry(a, b, i, d, e, box) || !tile_meets(t, box[0], box[1], box[2], box[3])) return false;
+        viz_entry_label(a, b, i, d, e);
+        return true;
+    });
+    if (cnt == 0) {
+        tile_copy_through<VIZ_TW>(t, c);
         return;
     }
-    for (int p = tid; p < VIZ_TW * VIZ_TH; p += VIZ_THREADS) {
+    // The pixels, by a loop of the kernel's own, as in redact_ops.hip: a shared skeleton that took the painting as a lambda cost the
+    // redaction's blur 0.8 % (profiles/r21_frame_tile.txt) and would have had this kernel as its only user.
+    const dbx_overlay_frame fm = t.fm;
+    const bool copying = fm.dst != fm.src;
+    for (int p = threadIdx.x; p < VIZ_TW * VIZ_TH; p += TILE_THREADS) {
         const int lx = p & (VIZ_TW - 1), ly = p / VIZ_TW;
-        if (lx >= cols || ly >= rows) continue;
-        const int x = x0 + lx, y = y0 + ly;
+        if (lx >= t.cols || ly >= t.rows) continue;
+        const int x = t.x0 + lx, y = t.y0 + ly;
         int kind = 0;
         const uint8_t* cp = nullptr;
         for (int k = cnt - 1; k >= 0 && !kind; --k) kind = viz_hit(list[k], a, b, x, y, &cp);
@@ -285,10 +238,9 @@ extern "C" int dbx_draw_overlay_batch(const dbx_overlay_frame* frames, int32_t b
     static_assert(sizeof(dbx_overlay_frame) == 24 && sizeof(dbx_overlay_style) == 28, "dbx_overlay_frame is 24 bytes, dbx_overlay_style 28");
     static_assert(sizeof(VizEnt) == 88, "a collected row is 88 bytes of LDS");
     const char* fn = "draw_overlay_batch";
-    const int rc = det_rows_check(fn, det_cols, det_rows, prefix, batch, slots, VIZ_MAX_SLOTS);
+    int rc = det_rows_check(fn, det_cols, det_rows, prefix, batch, slots, VIZ_MAX_SLOTS);
+    if (rc == DBX_OK) rc = tile_dims_check(fn, c, max_h, max_w);
     if (rc != DBX_OK) return rc;
-    DBX_REQUIRE(c >= 1 && c <= 4, "%s: c=%d must be 1..4", fn, c);
-    DBX_REQUIRE(max_h >= 1 && max_w >= 1, "%s: max_h=%d and max_w=%d must be positive", fn, max_h, max_w);
     DBX_REQUIRE(style, "%s: null style", fn);
     DBX_REQUIRE(style->thickness >= 1 && style->thickness <= 16, "%s: thickness=%d must be 1..16", fn, style->thickness);
     DBX_REQUIRE(style->radius >= -1 && style->radius <= 32, "%s: radius=%d must be -1..32", fn, style->radius);
@@ -297,25 +249,17 @@ extern "C" int dbx_draw_overlay_batch(const dbx_overlay_frame* frames, int32_t b
     DBX_REQUIRE((crops == nullptr) == (ok == nullptr), "%s: crops and ok must be given together", fn);
     DBX_REQUIRE(!crops || (ow >= 1 && oh >= 1), "%s: a crop of %d x %d pixels is empty", fn, ow, oh);
     DBX_REQUIRE(frames && dets && keep, "%s: null argument", fn);
-    const int64_t tiles_x = ((int64_t)max_w + VIZ_TW - 1) / VIZ_TW, tiles_y = ((int64_t)max_h + VIZ_TH - 1) / VIZ_TH;
-    DBX_REQUIRE(tiles_x * tiles_y < (1 << 24) && batch <= 65535, "%s: %lld tiles x %d frames exceed one grid (2^24 - 1 tiles, 65535 frames)", fn,
-                (long long)(tiles_x * tiles_y), batch);
-    if (batch == 0) return DBX_OK;
-    const size_t lds = viz_lds_bytes(slots);
-    if (lds > 32768) {
-        static DbxDevOnce attr_once; int attr_dev = 0;
-        if (attr_once.pending(&attr_dev)) {
-            DBX_HIP(hipFuncSetAttribute((const void*)draw_overlay_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)viz_lds_bytes(VIZ_MAX_SLOTS)));
-            attr_once.mark(attr_dev);
-        }
-    }
     VizArgs a;
+    dim3 grid;
+    rc = tile_grid<VIZ_TW, VIZ_TH>(fn, max_h, max_w, batch, &grid, &a.tiles_x);
+    if (rc != DBX_OK || batch == 0) return rc;
+    const size_t lds = viz_lds_bytes(slots);
+    rc = tile_lds_limit<draw_overlay_batch_kernel>(lds, viz_lds_bytes(VIZ_MAX_SLOTS));
+    if (rc != DBX_OK) return rc;
     a.frames = frames; a.dets = dets; a.keep = keep; a.prefix = prefix; a.track_id = track_id; a.crops = crops; a.ok = ok;
     a.det_rows = det_rows; a.st = *style; a.c = c; a.det_cols = det_cols; a.slots = slots; a.ow = ow; a.oh = oh;
-    a.max_h = max_h; a.max_w = max_w; a.tiles_x = (int)tiles_x;
-    hipLaunchKernelGGL(draw_overlay_batch_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)batch), dim3(VIZ_THREADS), lds,
-                       (hipStream_t)stream, a);
+    a.max_h = max_h; a.max_w = max_w;
+    hipLaunchKernelGGL(draw_overlay_batch_kernel, grid, dim3(TILE_THREADS), lds, (hipStream_t)stream, a);
     DBX_LAUNCH_CHECK();
     return DBX_OK;
 }

@@ -24,6 +24,7 @@ import torch
 
 import densebox_amd as D
 from densebox_amd import rows, synth, track, viz
+from densebox_amd.frames import overlay_table
 
 H, W, B, K = 512, 512, 32, 10
 
@@ -132,7 +133,7 @@ def main():
             keep[i, 0], keep[i, 1:1 + len(kl)], ids[i, :len(kl)] = len(kl), kl, tid
         keep, ids = torch.from_numpy(keep).cuda(), torch.from_numpy(ids).cuda()
         out = torch.empty_like(x)
-        table = viz.overlay_table(list(x.unbind(0)), list(out.unbind(0)))
+        table = overlay_table(list(x.unbind(0)), list(out.unbind(0)))
 
         drows = rows.Rows(d, keep, None, B, K)
 

@@ -23,7 +23,8 @@ import numpy as np
 import torch
 
 import densebox_amd as D
-from densebox_amd import redact, rows, synth, track, viz
+from densebox_amd import redact, rows, synth, track
+from densebox_amd.frames import overlay_table
 
 H, W, B, K = 512, 512, 32, 10
 
@@ -181,7 +182,7 @@ def main():
             keep[i, 0], keep[i, 1:1 + len(kl)] = len(kl), kl
         keep = torch.from_numpy(keep).cuda()
         out = torch.empty_like(x)
-        table = viz.overlay_table(list(x.unbind(0)), list(out.unbind(0)))
+        table = overlay_table(list(x.unbind(0)), list(out.unbind(0)))
         drows = rows.Rows(d, keep, None, B, K)
         state = tr_b._buffers(x.device)[0]
         tracks_at = state.data_ptr() + tr_b._layout()[0]
