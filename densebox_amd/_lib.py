@@ -117,6 +117,22 @@ class ResizeJob(C.Structure):
                 ('pad_b', C.c_int32), ('pad_value', C.c_int32), ('dh', C.c_int32), ('dw', C.c_int32), ('dst_off', C.c_int64)]
 
 
+class Nv12Frame(C.Structure):
+    _fields_ = [('y', C.c_void_p), ('uv', C.c_void_p), ('rgb', C.c_void_p), ('h', C.c_int32), ('w', C.c_int32), ('pitch_y', C.c_int32),
+                ('pitch_uv', C.c_int32), ('pitch_rgb', C.c_int32), ('reserved', C.c_int32)]
+
+
+class Nv12Params(C.Structure):
+    _fields_ = [('standard', C.c_int32), ('range', C.c_int32), ('order', C.c_int32), ('reserved', C.c_int32)]
+
+
+class ResizeJobNv12(C.Structure):
+    _fields_ = [('y', C.c_void_p), ('uv', C.c_void_p), ('pitch_y', C.c_int32), ('pitch_uv', C.c_int32), ('sh', C.c_int32),
+                ('sw', C.c_int32), ('cx0', C.c_int32), ('cy0', C.c_int32), ('cw', C.c_int32), ('ch', C.c_int32), ('pad_l', C.c_int32),
+                ('pad_t', C.c_int32), ('pad_r', C.c_int32), ('pad_b', C.c_int32), ('pad_value', C.c_int32), ('dh', C.c_int32),
+                ('dw', C.c_int32), ('dst_off', C.c_int64)]
+
+
 class PatchJob(C.Structure):
     _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('scale_x', C.c_double), ('scale_y', C.c_double), ('row_bytes', C.c_int32),
                 ('cx0', C.c_int32), ('cy0', C.c_int32), ('cw', C.c_int32), ('ch', C.c_int32), ('pad_l', C.c_int32), ('pad_t', C.c_int32),
@@ -239,6 +255,11 @@ SIGNATURES = {
     'dbx_redact_host': (C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP, _I32, _I32, _VP, _I32, _VP, _I32, C.POINTER(RedactStyle)]),
     'dbx_resize_batch_workspace_bytes': (_I64, [_I32]),
     'dbx_resize_cubic_batch_u8': (C.c_int, [C.POINTER(ResizeJob), _I32, _I32, _VP, _VP, _VP]),
+    'dbx_nv12_to_rgb_batch': (C.c_int, [_VP, _I32, _I32, _I32, C.POINTER(Nv12Params), _VP]),
+    'dbx_rgb_to_nv12_batch': (C.c_int, [_VP, _I32, _I32, _I32, C.POINTER(Nv12Params), _VP]),
+    'dbx_nv12_host': (C.c_int, [C.POINTER(Nv12Frame), C.POINTER(Nv12Params), _I32]),
+    'dbx_resize_batch_nv12_workspace_bytes': (_I64, [_I32]),
+    'dbx_resize_cubic_batch_nv12': (C.c_int, [C.POINTER(ResizeJobNv12), _I32, C.POINTER(Nv12Params), _VP, _VP, _VP]),
     'dbx_patch_plan': (C.c_int, [C.POINTER(PatchPlanIO), _I32, _I32, _I32, _I32, _I32, _D, _D, _I32, _VP]),
     'dbx_patch_cut': (C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP]),
     'dbx_patch_plan_host': (C.c_int, [_I32, _I32, _I32, _VP, _I32, _D, _D, _D, _I32, C.POINTER(PatchGeom)]),

@@ -239,7 +239,7 @@ __global__ __launch_bounds__(RSZ_THREADS) void patch_cut_kernel(const ResizeJobD
     const int cnt = *count;
     if (slot >= (cnt < n ? cnt : n)) return;           // uniform over the workgroup
     const int x0 = (tt % PATCH_TILES_X) * RSZ_TW, y0 = (tt / PATCH_TILES_X) * RSZ_TH;
-    resize_tile_body<C>(jobs + slot, patches + (size_t)slot * DBX_PATCH_SIDE * DBX_PATCH_SIDE * C, x0, y0);
+    resize_tile_body(jobs + slot, patches + (size_t)slot * DBX_PATCH_SIDE * DBX_PATCH_SIDE * C, x0, y0, RszSrcU8<C>(jobs + slot));
 }
 
 extern "C" int dbx_patch_plan(const dbx_patch_plan_io* io, int32_t n_frames, int32_t n_plates, int32_t c, int32_t M, int32_t n,

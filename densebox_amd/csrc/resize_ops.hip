@@ -25,7 +25,7 @@ __global__ __launch_bounds__(RSZ_THREADS) void resize_cubic_batch_u8_kernel(cons
     const ResizeJobDev* J = jobs + lo;
     const int tt = t - tile0[lo], tiles_x = J->tiles_x;
     const int x0 = (tt % tiles_x) * RSZ_TW, y0 = (tt / tiles_x) * RSZ_TH;
-    resize_tile_body<C>(J, J->dst, x0, y0);
+    resize_tile_body(J, J->dst, x0, y0, RszSrcU8<C>(J));
 }
 
 static int64_t resize_tile0_offset(int32_t njobs) { return (int64_t)njobs * (int64_t)sizeof(ResizeJobDev); }

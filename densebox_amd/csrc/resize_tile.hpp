@@ -1,6 +1,7 @@
-// The tile body of the batched bicubic resize, shared by resize_cubic_batch_u8_kernel (resize_ops.hip) and patch_cut_kernel
-// (patch_ops.hip): both kernels run THIS code on a device job record, so a patch is bit for bit the resize of its window.  The
-// including file turns floating-point contraction off (the coefficient arithmetic must give the bits NumPy gives).
+// The tile body of the batched bicubic resize, shared by resize_cubic_batch_u8_kernel (resize_ops.hip), patch_cut_kernel
+// (patch_ops.hip) and resize_cubic_batch_nv12_kernel (color_ops.hip): all run THIS code on a device job record, so a patch is bit for
+// bit the resize of its window and the resize of an NV12 surface bit for bit the resize of its converted frame.  The including file
+// turns floating-point contraction off (the coefficient arithmetic must give the bits NumPy gives).
 #pragma once
 #include "common.hpp"
 
@@ -45,6 +46,28 @@ __device__ __forceinline__ void cubic_taps(int d, double scale, int vn, int pad0
     }
 }
 
+// nb bytes of one tile row from LDS to global memory at g, by lanes q of 16: L holds byte b of the row at L[shift + b], shift = g & 15,
+// so that the row's aligned 16-byte words are stored as such; a word that is only partly inside the row (at most the first and the
+// last) falls back to its whole dwords, then to bytes, so no byte outside [g, g + nb) is written.
+__device__ __forceinline__ void rsz_store_row(rsz_gdst_t g, const unsigned char* L, int nb, int q16) {
+    const int shift = (int)((size_t)g & 15), end = shift + nb;
+    const rsz_gdst_t gw = g - shift;                   // 16-byte aligned; byte b of the row is gw[shift + b] = L[shift + b]
+    for (int k = q16; 16 * k < end; k += 16) {
+        const int b0 = 16 * k;
+        if (b0 >= shift && b0 + 16 <= end) {
+            reinterpret_cast<rsz_gdst4_t>(gw)[k] = reinterpret_cast<const u32x4*>(L)[k];
+        } else {
+            for (int j = b0; j < b0 + 16; j += 4) {
+                if (j >= shift && j + 4 <= end) {
+                    reinterpret_cast<rsz_gdst1_t>(gw)[j >> 2] = reinterpret_cast<const unsigned int*>(L)[j >> 2];
+                } else {
+                    for (int q = j < shift ? shift : j; q < j + 4 && q < end; ++q) gw[q] = L[q];
+                }
+            }
+        }
+    }
+}
+
 // One RSZ_TH x RSZ_TW tile at (x0, y0) of job J's destination, written behind `dst_base` (the job's [dh][dw][C] block).  All
 // RSZ_THREADS threads of the workgroup call it.
 //   1. Tables: the first RSZ_TW threads make the four 16-bit coefficients and the four source byte offsets (or -1: padding) of
@@ -56,8 +79,25 @@ __device__ __forceinline__ void cubic_taps(int d, double scale, int vn, int pad0
 //   3. Stores: 16 lanes per tile row store the row's aligned 16-byte words; a word that is only partly inside the row (at most
 //      the first and the last) falls back to its whole dwords, then to bytes, so no byte outside the job's block is written.
 // Source and destination go through global-address-space pointers (global_load / global_store, not flat).
-template <int C>
-__device__ __forceinline__ void resize_tile_body(const ResizeJobDev* __restrict__ J, unsigned char* dst_base, int x0, int y0) {
+// The taps come from a SOURCE POLICY `src`: C, the channel count; col_stride() / row_stride(), what one step along an axis adds to a
+// tap's offset; fetch(yo, xo, px), the C values of the tap at row offset yo and column offset xo, made ONCE per tap.  RszSrcU8 is the
+// interleaved uint8 image the resize and the patch cutter read; color_ops.hip adds the NV12 surface, whose fetch converts the tap.
+template <int C_> struct RszSrcU8 {
+    static constexpr int C = C_;
+    rsz_gsrc_t src;
+    int row_bytes;
+    __device__ __forceinline__ RszSrcU8(const ResizeJobDev* J) : src((rsz_gsrc_t)J->src), row_bytes(J->row_bytes) {}
+    __device__ __forceinline__ int col_stride() const { return C; }
+    __device__ __forceinline__ int row_stride() const { return row_bytes; }
+    __device__ __forceinline__ void fetch(int yo, int xo, int* px) const {
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) px[ch] = (int)src[yo + xo + ch];
+    }
+};
+
+template <class Src>
+__device__ __forceinline__ void resize_tile_body(const ResizeJobDev* __restrict__ J, unsigned char* dst_base, int x0, int y0, const Src src) {
+    constexpr int C = Src::C;
     constexpr int ROW = RSZ_TW * C + 16;               // a tile row in LDS: its bytes after a shift of 0..15
     __shared__ __attribute__((aligned(16))) unsigned char stage[RSZ_TH][ROW];
     __shared__ short col_a[RSZ_TW][4], row_a[RSZ_TH][4];
@@ -66,16 +106,15 @@ __device__ __forceinline__ void resize_tile_body(const ResizeJobDev* __restrict_
     const int dh = J->dh, dw = J->dw;
     if (tid < RSZ_TW) {
         const int x = x0 + tid < dw ? x0 + tid : dw - 1;
-        cubic_taps(x, J->scale_x, J->vw, J->pad_l, J->cw, J->cx0, C, col_a[tid], col_o[tid]);
+        cubic_taps(x, J->scale_x, J->vw, J->pad_l, J->cw, J->cx0, src.col_stride(), col_a[tid], col_o[tid]);
     } else if (tid < RSZ_TW + RSZ_TH) {
         const int r = tid - RSZ_TW, y = y0 + r < dh ? y0 + r : dh - 1;
-        cubic_taps(y, J->scale_y, J->vh, J->pad_t, J->ch, J->cy0, J->row_bytes, row_a[r], row_o[r]);
+        cubic_taps(y, J->scale_y, J->vh, J->pad_t, J->ch, J->cy0, src.row_stride(), row_a[r], row_o[r]);
     }
     __syncthreads();
     const rsz_gdst_t dst = (rsz_gdst_t)dst_base;
     {
         const int lane = tid & 63, wave = tid >> 6, x = x0 + lane;
-        const rsz_gsrc_t src = (rsz_gsrc_t)J->src;
         const int pv = J->pad_value;
         int a[4], xo[4];
 #pragma unroll
@@ -97,9 +136,12 @@ __device__ __forceinline__ void resize_tile_body(const ResizeJobDev* __restrict_
                 for (int ch = 0; ch < C; ++ch) h[ch] = 0;
 #pragma unroll
                 for (int kx = 0; kx < 4; ++kx) {
-                    const bool padded = (xo[kx] | yo) < 0;
+                    int px[C];
 #pragma unroll
-                    for (int ch = 0; ch < C; ++ch) h[ch] += a[kx] * (padded ? pv : (int)src[yo + xo[kx] + ch]);
+                    for (int ch = 0; ch < C; ++ch) px[ch] = pv;
+                    if ((xo[kx] | yo) >= 0) src.fetch(yo, xo[kx], px);
+#pragma unroll
+                    for (int ch = 0; ch < C; ++ch) h[ch] += a[kx] * px[ch];
                 }
 #pragma unroll
                 for (int ch = 0; ch < C; ++ch) acc[ch] += b * h[ch];
@@ -116,22 +158,5 @@ __device__ __forceinline__ void resize_tile_body(const ResizeJobDev* __restrict_
     const int r = tid >> 4, y = y0 + r;
     if (y >= dh) return;
     const int nb = (dw - x0 < RSZ_TW ? dw - x0 : RSZ_TW) * C;
-    const rsz_gdst_t g = dst + ((long long)y * dw + x0) * C;
-    const int shift = (int)((size_t)g & 15), end = shift + nb;
-    const rsz_gdst_t gw = g - shift;                   // 16-byte aligned; byte b of the row is gw[shift + b] = stage[r][shift + b]
-    const unsigned char* L = stage[r];
-    for (int k = tid & 15; 16 * k < end; k += 16) {
-        const int b0 = 16 * k;
-        if (b0 >= shift && b0 + 16 <= end) {
-            reinterpret_cast<rsz_gdst4_t>(gw)[k] = reinterpret_cast<const u32x4*>(L)[k];
-        } else {
-            for (int j = b0; j < b0 + 16; j += 4) {
-                if (j >= shift && j + 4 <= end) {
-                    reinterpret_cast<rsz_gdst1_t>(gw)[j >> 2] = reinterpret_cast<const unsigned int*>(L)[j >> 2];
-                } else {
-                    for (int q = j < shift ? shift : j; q < j + 4 && q < end; ++q) gw[q] = L[q];
-                }
-            }
-        }
-    }
+    rsz_store_row(dst + ((long long)y * dw + x0) * C, stage[r], nb, tid & 15);
 }

@@ -585,9 +585,15 @@ def detect_batch_resized(net, images, size=720, K=10, nms_thresh=0.4, max_batch=
     host, _ = rectify.host_images('detect_batch_resized', images, 3)
     x = resize._pad_resize_device(rectify.to_device(images, host), int(size))
     res = detect_batch(net, x, K, nms_thresh, max_batch) if tc is None else detect_batch_thresh(net, x, tc[0], tc[1], nms_thresh, max_batch)
+    return _map_back([(im.size(0), im.size(1)) for im in host], res, size)
+
+
+def _map_back(hw, res, size):
+    """detect_batch_resized's rows in source-frame coordinates: hw[b] = (H, W) of frame b, res[b] = (dets, keep) on its resized frame"""
+    from . import resize
     out = []
-    for im, (d, keep) in zip(host, res):
-        side, pad_x, pad_y = resize.pad_geometry(im.size(0), im.size(1))
+    for (h, w), (d, keep) in zip(hw, res):
+        side, pad_x, pad_y = resize.pad_geometry(h, w)
         s = side / int(size)
         d = d.copy()
         xs = [0, 2] + list(range(5, d.shape[1], 2))

@@ -196,6 +196,26 @@ class _DenseBoxBase(nn.Module):
         from .decode import detect_batch_resized
         return detect_batch_resized(self, images, size, K, nms_thresh, max_batch, score_thresh, max_dets)
 
+    def detect_batch_nv12(self, frames, width=None, params=None, K=10, nms_thresh=0.4, max_batch=32):
+        """detect_batch() on NV12 frames of one size ([h*3/2, pitch] uint8 each, see densebox_amd.color): one conversion launch, then
+        detect_batch's tensor path; a list of (dets, keep) in input order (densebox_amd.color.detect_batch_nv12)."""
+        from .color import detect_batch_nv12
+        return detect_batch_nv12(self, frames, width, params, K, nms_thresh, max_batch)
+
+    def detect_batch_resized_nv12(self, frames, size=720, width=None, params=None, K=10, nms_thresh=0.4, max_batch=32, score_thresh=None,
+                                  max_dets=1024):
+        """detect_batch_resized() on NV12 frames of any sizes: pad + bicubic resize read the NV12 surfaces in one fused launch; a list
+        of (dets, keep) in input order, coordinates mapped back to the source frames (densebox_amd.color.detect_batch_resized_nv12)."""
+        from .color import detect_batch_resized_nv12
+        return detect_batch_resized_nv12(self, frames, size, width, params, K, nms_thresh, max_batch, score_thresh, max_dets)
+
+    def redact_batch_nv12(self, frames, *, width=None, tracker=None, stream0=0, K=10, nms_thresh=0.4, max_batch=32, style=None, params=None):
+        """redact_batch() with NV12 frames in and redacted NV12 frames out, converted on the device on both sides: a list of
+        (dets, keep, track_id or None, nv12 [h*3/2, w]) in input order (densebox_amd.color.redact_batch_nv12)."""
+        from .color import redact_batch_nv12
+        return redact_batch_nv12(self, frames, width=width, tracker=tracker, stream0=stream0, K=K, nms_thresh=nms_thresh,
+                                 max_batch=max_batch, style=style, params=params)
+
     def detect_pyramid(self, images, sizes=(480, 720, 1080), K=10, nms_thresh=0.4, max_batch=32, score_thresh=None, max_dets=1024,
                        with_levels=False):
         """detect_batch_resized() at every size of `sizes` with one resize launch, the rows of all levels merged in source-frame

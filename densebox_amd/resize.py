@@ -132,24 +132,86 @@ def crop_resize_batch(images, windows, size=(240, 240)):
     image-then-window order."""
     dw, dh = _check_size('crop_resize_batch', size)
     host, _ = host_images('crop_resize_batch', images, None)
-    if not isinstance(windows, (list, tuple)) or len(windows) != len(host):
-        raise RuntimeError('crop_resize_batch: %s lists of windows for %d images'
-                           % (len(windows) if isinstance(windows, (list, tuple)) else 'no', len(host)))
+    spec = _window_spec('crop_resize_batch', [(int(im.size(0)), int(im.size(1))) for im in host], windows, dh, dw)
+    return _resize_jobs(to_device(images, host), spec, int(host[0].size(2)))
+
+
+def _window_spec(fn, hw, windows, dh, dw):
+    """the job tuples of windows[b] on image b of hw[b] = (h, w) pixels, each resized to dh x dw"""
+    if not isinstance(windows, (list, tuple)) or len(windows) != len(hw):
+        raise RuntimeError('%s: %s lists of windows for %d images' % (fn, len(windows) if isinstance(windows, (list, tuple)) else 'no', len(hw)))
     spec = []
-    for b, (im, wins) in enumerate(zip(host, windows)):
-        h, w = int(im.size(0)), int(im.size(1))
+    for b, ((h, w), wins) in enumerate(zip(hw, windows)):
         for win in wins:
             try:
                 x0, y0, x1, y1 = (int(v) for v in win)
                 if any(int(v) != v for v in win):
                     raise ValueError
             except (TypeError, ValueError):
-                raise RuntimeError('crop_resize_batch: a window must be 4 integers (x0, y0, x1, y1), got %r for image %d' % (win, b))
+                raise RuntimeError('%s: a window must be 4 integers (x0, y0, x1, y1), got %r for image %d' % (fn, win, b))
             xa, xb, _ = slice(x0, x1).indices(w)
             ya, yb, _ = slice(y0, y1).indices(h)
             if xb <= xa or yb <= ya:
-                raise RuntimeError('crop_resize_batch: window %r of image %d (%d x %d) is an empty slice' % (tuple(win), b, h, w))
+                raise RuntimeError('%s: window %r of image %d (%d x %d) is an empty slice' % (fn, tuple(win), b, h, w))
             spec.append((b, xa, ya, xb - xa, yb - ya, 0, 0, 0, 0, dh, dw))
     if not spec:
-        raise RuntimeError('crop_resize_batch: no windows')
-    return _resize_jobs(to_device(images, host), spec, int(host[0].size(2)))
+        raise RuntimeError('%s: no windows' % fn)
+    return spec
+
+
+# ------------------------------------------------------------------------------------------------------------ NV12 sources
+def _resize_jobs_nv12(fr, spec, params):
+    """_resize_jobs on NV12 surfaces: ONE upload of the frames that are on the host and ONE dbx_resize_cubic_batch_nv12 launch over
+    spec (job tuples as _resize_jobs takes them, b indexing the checked color._Frame list fr); the uint8 [len(spec), dh, dw, 3] CUDA
+    tensor.  The converted full-resolution frame is never written."""
+    from . import color
+    dh, dw = spec[0][9], spec[0][10]
+    up = color._Upload([f.t for f in fr], 0)
+    up.send()
+    out = torch.empty((len(spec), dh, dw, 3), dtype=torch.uint8, device=up.dev)
+    jobs = (_lib.ResizeJobNv12 * len(spec))()
+    for i, (r, (b, cx0, cy0, cw, ch, pl, pt, pr, pb, jh, jw)) in enumerate(zip(jobs, spec)):
+        f = fr[b]
+        r.y, r.uv, r.pitch_y, r.pitch_uv, r.sh, r.sw = up.base[b], up.base[b] + f.h * f.pitch, f.pitch, f.pitch, f.h, f.w
+        r.cx0, r.cy0, r.cw, r.ch = cx0, cy0, cw, ch
+        r.pad_l, r.pad_t, r.pad_r, r.pad_b, r.pad_value = pl, pt, pr, pb, PAD_VALUE
+        r.dh, r.dw, r.dst_off = jh, jw, i * dh * dw * 3
+    L = _lib.lib()
+    ws = torch.empty(L.dbx_resize_batch_nv12_workspace_bytes(len(spec)), dtype=torch.uint8, device=up.dev)
+    check(L.dbx_resize_cubic_batch_nv12(jobs, len(spec), C.byref(params.record()), C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()),
+                                        stream_ptr()))
+    return out
+
+
+def _pad_resize_nv12_device(fr, size, params):
+    """pad_resize_batch_nv12 on checked frames"""
+    spec = []
+    for b, f in enumerate(fr):
+        side, px, py = pad_geometry(f.h, f.w)
+        spec.append((b, 0, 0, f.w, f.h, px, py, side - f.w - px, side - f.h - py, size, size))
+    return _resize_jobs_nv12(fr, spec, params)
+
+
+def pad_resize_batch_nv12(frames, size=720, width=None, params=None):
+    """pad_resize_batch on NV12 frames in ONE fused launch (dbx_resize_cubic_batch_nv12): bit for bit
+    pad_resize_batch(color.nv12_to_rgb_batch(frames, width, params), size), but every tap is fetched from the NV12 surface and converted
+    on the fly -- 1.5 source bytes per pixel in the place of 3, and no full-resolution RGB frame.  frames, width, params: as for
+    color.nv12_to_rgb_batch.  Returns a uint8 [B, size, size, 3] CUDA tensor."""
+    from . import color
+    fn = 'pad_resize_batch_nv12'
+    if not isinstance(size, (int, np.integer)) or size < 1:
+        raise RuntimeError('%s: size must be a positive integer (the side of the square), got %r' % (fn, size))
+    p = color._params(fn, params)
+    return _pad_resize_nv12_device(color._frames(fn, frames, width), int(size), p)
+
+
+def crop_resize_batch_nv12(frames, windows, size=(240, 240), width=None, params=None):
+    """crop_resize_batch on NV12 frames in ONE fused launch: per frame b and window (x0, y0, x1, y1) of windows[b] (integers with
+    Python-slice semantics; odd coordinates are fine: chroma is indexed by absolute source coordinates), the bicubic resize of the
+    converted window to size = (width, height).  Returns a uint8 [P, height, width, 3] CUDA tensor in frame-then-window order."""
+    from . import color
+    fn = 'crop_resize_batch_nv12'
+    dw, dh = _check_size(fn, size)
+    p = color._params(fn, params)
+    fr = color._frames(fn, frames, width)
+    return _resize_jobs_nv12(fr, _window_spec(fn, [(f.h, f.w) for f in fr], windows, dh, dw), p)

@@ -76,7 +76,10 @@ const char* dbx_last_error(void);
  *      also at 13, without a bump: dbx_patch_warp_rec, dbx_patch_warp_cfg, dbx_patch_warp_io, dbx_patch_warp_plan, dbx_patch_warp,
  *      dbx_patch_warp_params_host, dbx_patch_warp_host (training patches warped on the device), pure additions likewise
  *      also at 13, without a bump: dbx_redact_style, dbx_redact_batch, dbx_redact_host (plates made unreadable on the device), pure
- *      additions likewise */
+ *      additions likewise
+ *      also at 13, without a bump: dbx_nv12_frame, dbx_nv12_params, dbx_resize_job_nv12, dbx_nv12_to_rgb_batch, dbx_rgb_to_nv12_batch,
+ *      dbx_nv12_host, dbx_resize_batch_nv12_workspace_bytes, dbx_resize_cubic_batch_nv12 (NV12 frames converted to and from RGB and
+ *      resized straight from the surface), pure additions likewise */
 #define DBX_ABI_VERSION 13
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
@@ -1022,6 +1025,100 @@ typedef struct dbx_resize_job {
 } dbx_resize_job;
 int64_t dbx_resize_batch_workspace_bytes(int32_t njobs);
 int dbx_resize_cubic_batch_u8(const dbx_resize_job* jobs, int32_t njobs, int32_t c, uint8_t* dst, void* workspace, void* stream);
+
+/* ---- NV12 frames in and out (no reference counterpart): what a video decoder hands out and an encoder takes, converted to and from
+ * the interleaved uint8 RGB every other entry point reads, and resized straight from the NV12 surface.  The semantics are this project's
+ * own, restated in NumPy by tests/nv12_ref.py ----
+ * An NV12 frame of h x w pixels, h and w both even: a Y plane of h rows of pitch_y >= w bytes and a UV plane of h / 2 rows of
+ * pitch_uv >= w bytes holding U0 V0 U1 V1 ...  Pixel (x, y) uses Y[y][x], U = UV[y >> 1][x & ~1] and V = UV[y >> 1][(x & ~1) + 1]:
+ * chroma is REPLICATED over its 2 x 2 block.  There is NO chroma interpolation, in either direction.  The RGB image is interleaved
+ * [h][pitch_rgb bytes] with pitch_rgb >= 3 * w.  Every pointer and every pitch may have any byte alignment.
+ * dbx_nv12_params: standard 601 or 709 (Kr, Kb = 0.299, 0.114 or 0.2126, 0.0722; Kg = 1 - Kr - Kb), range 0 limited (Y 16..235, chroma
+ * 16..240) or 1 full, order 0 RGB or 1 BGR (the byte order of a pixel of the interleaved image; the engine's uint8 input is RGB).
+ * All arithmetic is 14-bit integer: every coefficient is rint(c * 16384) of the float64 constant, and >> is the arithmetic shift (floor).
+ * To RGB: ys, cs, yo = 255/219, 255/224, 16 (limited) or 1, 1, 0 (full); C = Y - yo, D = U - 128, E = V - 128;
+ *   R = clip8((ky*C + rv*E + 8192) >> 14), G = clip8((ky*C + gu*D + gv*E + 8192) >> 14), B = clip8((ky*C + bu*D + 8192) >> 14)
+ *   with ky = ys, rv = cs*2(1-Kr), gu = -cs*2Kb(1-Kb)/Kg, gv = -cs*2Kr(1-Kr)/Kg, bu = cs*2(1-Kb): the DBX_NV12_*_TO_RGB integers below.
+ * From RGB: ys', cs' = 219/255, 224/255 (limited) or 1, 1 (full).  Per pixel Y = clip8(((yr*R + yg*G + yb*B + 8192) >> 14) + yo) with
+ *   (yr, yg, yb) = ys' * (Kr, Kg, Kb).  Per 2 x 2 block, with the sums Rs, Gs, Bs of its four pixels (0..1020):
+ *   U = clip8(((ur*Rs + ug*Gs + ub*Bs + 32768) >> 16) + 128), V = clip8(((vr*Rs + vg*Gs + vb*Bs + 32768) >> 16) + 128) with
+ *   (ur, ug, ub) = cs' * (-Kr, -Kg, 1-Kb) / (2(1-Kb)) and (vr, vg, vb) = cs' * (1-Kr, -Kg, -Kb) / (2(1-Kr)): the DBX_NV12_*_FROM_RGB
+ *   integers below, in the order yr, yg, yb, ur, ug, ub, vr, vg, vb.  The rounded chroma rows sum to exactly 0 in all four variants, so
+ *   grey gives U = V = 128; the luma rows sum to 14071 (limited) or 16384 (full).
+ * Each result is within 1 of the float64 formula rounded to nearest.  The round trip is NOT the identity: chroma is averaged over 2 x 2
+ * blocks on the way out and replicated on the way back, limited range has fewer than 256 levels, and both directions round.
+ *
+ * dbx_nv12_to_rgb_batch / dbx_rgb_to_nv12_batch: ONE launch over a DEVICE table of `batch` dbx_nv12_frame records, a workgroup of 256
+ * threads per 128 x 16 tile on a grid of (the tiles of a max_h x max_w frame, batch); nothing is copied from the host and nothing
+ * synchronises.  to_rgb reads y and uv and writes rgb, from_rgb reads rgb and writes y and uv; for every frame not skipped every byte
+ * of the w (3 * w) bytes of every output row is written and nothing else: not the pitch gap behind a row, nothing outside the planes.
+ * A record is skipped, with nothing of it written, when a pointer is null, h or w is non-positive or odd, h > max_h or w > max_w, or
+ * a pitch is below its row (pitch_y < w, pitch_uv < w, pitch_rgb < 3 * w).  Device data is never trusted as a bound beyond that.
+ * Kernel shape: half of the workgroup's lanes own 8 x 2 pixels each -- four whole 2 x 2 blocks, so each UV pair is loaded (written)
+ * once -- and move the Y and UV bytes as one 8-byte word per row where the address allows, else as two dwords, else as bytes (also for
+ * the ragged last lane of a row).  The RGB side is staged in LDS, every tile row at the offset its global address has inside a 16-byte
+ * word, and moved by 16 lanes per row as aligned 16-byte words, with a dword and then a byte fall-back for the partial first and last
+ * word of a row (the store of the resize tile, csrc/resize_tile.hpp).  4.5 bytes move per pixel in either direction; no scratch, no atomics.
+ * Refused with DBX_ERR_ARG before anything is queued: batch < 0, max_h or max_w < 1, a null frames or params, standard not 601 or 709,
+ * range or order outside 0..1, more than 2^24 - 1 tiles or 65535 frames (one grid).  batch == 0: no-op.
+ * dbx_nv12_frame is 48 bytes (y 0, uv 8, rgb 16, h 24, w 28, pitch_y 32, pitch_uv 36, pitch_rgb 40, reserved 44); dbx_nv12_params is
+ * 16 bytes (standard 0, range 4, order 8, reserved 12).
+ *
+ * dbx_nv12_host: the same pixel functions compiled for the host (no GPU needed) on ONE frame whose pointers are host memory;
+ * direction 0 converts to RGB, 1 from RGB.  It REFUSES what the launches skip (a null pointer, a non-positive or odd size, a pitch
+ * below its row), a null frame or params, a bad enum and a direction outside 0..1.
+ *
+ * dbx_resize_cubic_batch_nv12: dbx_resize_cubic_batch_u8 with c = 3 whose virtual source is the CONVERTED frame, never materialised: a
+ * tap inside the crop is fetched as Y, U, V and converted, once per tap (16 conversions per output pixel, not 48); a padded tap
+ * contributes pad_value in all three channels.  The result is bit for bit dbx_resize_cubic_batch_u8 on dbx_nv12_to_rgb_batch's output.
+ * dbx_resize_job_nv12 is dbx_resize_job with y, uv, pitch_y, pitch_uv in the place of src; sh and sw are even; the crop window may start
+ * at odd coordinates and have odd sizes, because chroma is indexed by absolute source coordinates.  The workspace
+ * (dbx_resize_batch_nv12_workspace_bytes(njobs) device bytes) and the life times are dbx_resize_cubic_batch_u8's.  Refused with
+ * DBX_ERR_ARG before anything is queued: what dbx_resize_cubic_batch_u8 refuses (with both planes in the place of src and pitch_y * sh
+ * in the place of the image's bytes), odd or non-positive sh or sw, pitch_y < sw, pitch_uv < sw, and bad params.
+ * Layout (88 bytes): y 0, uv 8, pitch_y 16, pitch_uv 20, sh 24, sw 28, cx0 32, cy0 36, cw 40, ch 44, pad_l 48, pad_t 52, pad_r 56,
+ * pad_b 60, pad_value 64, dh 68, dw 72, (4 bytes of alignment padding,) dst_off 80. */
+#define DBX_NV12_601_LIMITED_TO_RGB 19077, 26149, -6419, -13320, 33050
+#define DBX_NV12_601_FULL_TO_RGB 16384, 22970, -5638, -11700, 29032
+#define DBX_NV12_709_LIMITED_TO_RGB 19077, 29372, -3494, -8731, 34610
+#define DBX_NV12_709_FULL_TO_RGB 16384, 25802, -3069, -7670, 30402
+#define DBX_NV12_601_LIMITED_FROM_RGB 4207, 8260, 1604, -2428, -4768, 7196, 7196, -6026, -1170
+#define DBX_NV12_601_FULL_FROM_RGB 4899, 9617, 1868, -2765, -5427, 8192, 8192, -6860, -1332
+#define DBX_NV12_709_LIMITED_FROM_RGB 2991, 10064, 1016, -1649, -5547, 7196, 7196, -6536, -660
+#define DBX_NV12_709_FULL_FROM_RGB 3483, 11718, 1183, -1877, -6315, 8192, 8192, -7441, -751
+typedef struct dbx_nv12_frame {
+    uint8_t* y;                              /* [h][pitch_y] */
+    uint8_t* uv;                             /* [h / 2][pitch_uv], U0 V0 U1 V1 ... */
+    uint8_t* rgb;                            /* [h][pitch_rgb], interleaved */
+    int32_t h, w;                            /* both even */
+    int32_t pitch_y, pitch_uv, pitch_rgb;    /* bytes per row: >= w, >= w, >= 3 * w */
+    int32_t reserved;
+} dbx_nv12_frame;
+typedef struct dbx_nv12_params {
+    int32_t standard;                        /* 601 or 709 */
+    int32_t range;                           /* 0 limited, 1 full */
+    int32_t order;                           /* 0 RGB, 1 BGR */
+    int32_t reserved;
+} dbx_nv12_params;
+typedef struct dbx_resize_job_nv12 {
+    const uint8_t* y;                        /* device Y plane [sh][pitch_y] */
+    const uint8_t* uv;                       /* device UV plane [sh / 2][pitch_uv] */
+    int32_t pitch_y, pitch_uv;
+    int32_t sh, sw;                          /* both even */
+    int32_t cx0, cy0, cw, ch;                /* crop window inside the frame; may be odd */
+    int32_t pad_l, pad_t, pad_r, pad_b;      /* constant padding around the crop */
+    int32_t pad_value;                       /* 0..255, in all three channels */
+    int32_t dh, dw;                          /* destination size */
+    int64_t dst_off;                         /* byte offset of this job's [dh][dw][3] output in dst */
+} dbx_resize_job_nv12;
+int dbx_nv12_to_rgb_batch(const dbx_nv12_frame* frames, int32_t batch, int32_t max_h, int32_t max_w, const dbx_nv12_params* params,
+                          void* stream);
+int dbx_rgb_to_nv12_batch(const dbx_nv12_frame* frames, int32_t batch, int32_t max_h, int32_t max_w, const dbx_nv12_params* params,
+                          void* stream);
+int dbx_nv12_host(const dbx_nv12_frame* frame, const dbx_nv12_params* params, int32_t direction);
+int64_t dbx_resize_batch_nv12_workspace_bytes(int32_t njobs);
+int dbx_resize_cubic_batch_nv12(const dbx_resize_job_nv12* jobs, int32_t njobs, const dbx_nv12_params* params, uint8_t* dst,
+                                void* workspace, void* stream);
 
 /* ---- training patch sampling (gen_pos_patch, process_plate.py:167-352, with format_4_vertices :109 and bbox_from_vertices :1247; the
  * negative path of gen_pure_neg_patches :711-749 with intersect_small :639-666) ----
