@@ -4,42 +4,35 @@
 // suite (dbx_patch_aug_params_host, dbx_patch_augment_host).
 #include "common.hpp"
 #include "patch_hash.hpp"
+#include "patch_stage.hpp"
 
 static_assert(sizeof(dbx_patch_aug) == 64 && sizeof(dbx_patch_aug_cfg) == 112 && sizeof(dbx_patch_aug_io) == 72, "augmentation ABI layouts");
 static_assert(offsetof(dbx_patch_aug, key_lo) == 32 && offsetof(dbx_patch_aug, gain) == 40 && offsetof(dbx_patch_aug_cfg, kind_w) == 32 &&
               offsetof(dbx_patch_aug_cfg, box_lo) == 44 && offsetof(dbx_patch_aug_cfg, G) == 100, "augmentation ABI layouts");
 
-#define AUG_THREADS 256
-#define AUG_SIDE DBX_PATCH_SIDE
-#define AUG_BAND 16
-#define AUG_BANDS (AUG_SIDE / AUG_BAND)
 #define AUG_HALO 2
-#define AUG_MAX_N 4096
 #define AUG_MAX_G 65536
 #define AUG_Q_MAX 65535
 
-__host__ __device__ inline int aug_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__host__ __device__ inline int aug_u8(int v) { return aug_clamp(v, 0, 255); }
+__host__ __device__ inline int aug_u8(int v) { return patch_clamp(v, 0, 255); }
 
 // what a kernel reads of a record
 __host__ __device__ inline void aug_sanitize(dbx_patch_aug* a, int G) {
     a->flags &= 3;
     if (a->blur < 0 || a->blur > 3) a->blur = 0;
     if (a->blur == 3 && (a->box_len < 3 || a->box_len > 9 || !(a->box_len & 1))) a->blur = 0;
-    a->sat = aug_clamp(a->sat, 0, AUG_Q_MAX);
-    a->contrast = aug_clamp(a->contrast, 0, AUG_Q_MAX);
-    a->brightness = aug_clamp(a->brightness, -255, 255);
+    a->sat = patch_clamp(a->sat, 0, AUG_Q_MAX);
+    a->contrast = patch_clamp(a->contrast, 0, AUG_Q_MAX);
+    a->brightness = patch_clamp(a->brightness, -255, 255);
     if (a->curve < 0 || a->curve >= G) a->curve = -1;
-    a->noise_amp = aug_clamp(a->noise_amp, 0, AUG_Q_MAX);
-    for (int k = 0; k < 3; ++k) { a->gain[k] = aug_clamp(a->gain[k], 0, AUG_Q_MAX); a->reserved[k] = 0; }
+    a->noise_amp = patch_clamp(a->noise_amp, 0, AUG_Q_MAX);
+    for (int k = 0; k < 3; ++k) { a->gain[k] = patch_clamp(a->gain[k], 0, AUG_Q_MAX); a->reserved[k] = 0; }
 }
 
 __host__ __device__ inline bool aug_identity(const dbx_patch_aug& a, int c) {
     return !(a.flags & 1) && a.blur == 0 && (c < 3 || a.sat == 256) && a.contrast == 256 && a.brightness == 0 && a.curve < 0 &&
            a.noise_amp == 0 && a.gain[0] == 256 && a.gain[1] == 256 && a.gain[2] == 256;
 }
-
-__host__ __device__ inline int aug_range(uint64_t h, int lo, int hi) { return lo + (int)((h >> 11) % (uint64_t)(hi - lo + 1)); }
 
 // the record of slot s in device mode: a fixed draw number per field
 __host__ __device__ inline void aug_draw(const dbx_patch_aug_cfg& f, int64_t seed, int64_t counter, int s, dbx_patch_aug* a) {
@@ -53,18 +46,18 @@ __host__ __device__ inline void aug_draw(const dbx_patch_aug_cfg& f, int64_t see
     }
     a->blur = blur_on ? kind : 0;
     a->box_len = f.box_lo + 2 * (int)((patch_hash(seed, counter, s, 3) >> 11) % (uint64_t)((f.box_hi - f.box_lo) / 2 + 1));
-    a->sat = aug_range(patch_hash(seed, counter, s, 4), f.sat_lo, f.sat_hi);
-    a->contrast = aug_range(patch_hash(seed, counter, s, 5), f.contrast_lo, f.contrast_hi);
-    a->brightness = aug_range(patch_hash(seed, counter, s, 6), f.brightness_lo, f.brightness_hi);
+    a->sat = patch_range(patch_hash(seed, counter, s, 4), f.sat_lo, f.sat_hi);
+    a->contrast = patch_range(patch_hash(seed, counter, s, 5), f.contrast_lo, f.contrast_hi);
+    a->brightness = patch_range(patch_hash(seed, counter, s, 6), f.brightness_lo, f.brightness_hi);
     const bool curve_on = patch_unit(patch_hash(seed, counter, s, 7)) < f.p_curve;
-    a->curve = curve_on ? aug_range(patch_hash(seed, counter, s, 8), f.curve_lo, f.curve_hi) : -1;
+    a->curve = curve_on ? patch_range(patch_hash(seed, counter, s, 8), f.curve_lo, f.curve_hi) : -1;
     const bool noise_on = patch_unit(patch_hash(seed, counter, s, 9)) < f.p_noise;
-    a->noise_amp = noise_on ? aug_range(patch_hash(seed, counter, s, 10), f.noise_lo, f.noise_hi) : 0;
+    a->noise_amp = noise_on ? patch_range(patch_hash(seed, counter, s, 10), f.noise_lo, f.noise_hi) : 0;
     const uint64_t key = patch_hash(seed, counter, s, 11);
     a->key_lo = (int32_t)(uint32_t)key;
     a->key_hi = (int32_t)(uint32_t)(key >> 32);
     for (int k = 0; k < 3; ++k) {
-        a->gain[k] = aug_range(patch_hash(seed, counter, s, 12 + k), f.gain_lo, f.gain_hi);
+        a->gain[k] = patch_range(patch_hash(seed, counter, s, 12 + k), f.gain_lo, f.gain_hi);
         a->reserved[k] = 0;
     }
 }
@@ -76,13 +69,12 @@ __host__ __device__ inline void aug_plan_slot(const dbx_patch_aug_cfg& f, const 
     else aug_draw(f, seed, counter, s, a);
     aug_sanitize(a, f.G);
     a->flags &= 1;                                     // bit 1 is decided here
-    bool negative = true;
-    for (int k = 0; k < 12; ++k) { lout[k] = lin[k]; negative = negative && lin[k] == 0; }
-    if (!(a->flags & 1) || negative) return;
+    for (int k = 0; k < 12; ++k) lout[k] = lin[k];
+    if (!(a->flags & 1) || patch_row_negative(lin)) return;
     const int xs[6] = {lin[0], lin[2], lin[4], lin[6], lin[8], lin[10]};
     for (int k = 0; k < 6; ++k)
-        if (xs[k] < 0 || xs[k] > AUG_SIDE - 1) { a->flags = 2; return; }
-    const int m = AUG_SIDE - 1;
+        if (xs[k] < 0 || xs[k] > PATCH_SIDE - 1) { a->flags = 2; return; }
+    const int m = PATCH_SIDE - 1;
     lout[0] = m - lin[2]; lout[2] = m - lin[0];
     lout[4] = m - lin[6]; lout[5] = lin[7];            // lu' from ru
     lout[6] = m - lin[4]; lout[7] = lin[5];            // ru' from lu
@@ -90,15 +82,18 @@ __host__ __device__ inline void aug_plan_slot(const dbx_patch_aug_cfg& f, const 
     lout[10] = m - lin[8]; lout[11] = lin[9];          // ld' from rd
 }
 
-__host__ __device__ inline void aug_write_slot(const dbx_patch_aug& a, const int32_t* lab, int s, dbx_patch_aug* params, int32_t* labels,
-                                               float* bbox, float* vertices, float* label) {
-    params[s] = a;
-    bool negative = true;
-    for (int k = 0; k < 12; ++k) { labels[12 * s + k] = lab[k]; negative = negative && lab[k] == 0; }
-    for (int k = 0; k < 4; ++k) bbox[4 * s + k] = (float)((double)lab[k] / 4.0);
-    for (int k = 0; k < 8; ++k) vertices[8 * s + k] = (float)((double)lab[4 + k] / 4.0);
-    label[s] = negative ? 0.0f : 1.0f;
-}
+// patch_stage.hpp's policy: the plan kernel and its host loop over aug_plan_slot
+struct AugStage {
+    typedef dbx_patch_aug_io io_t;
+    typedef dbx_patch_aug_cfg cfg_t;
+    __host__ __device__ static void slot(const io_t& io, const cfg_t& f, bool device_mode, int64_t seed, int64_t counter, int s) {
+        dbx_patch_aug a;
+        int32_t lab[12];
+        aug_plan_slot(f, device_mode ? nullptr : io.params_in + s, seed, counter, s, io.labels_in + 12 * s, &a, lab);
+        io.params[s] = a;
+        patch_write_labels(lab, s, io.labels, io.bbox, io.vertices, io.label, patch_row_negative(lab));
+    }
+};
 
 // entry v of colour channel k's tone table
 __host__ __device__ inline int aug_tone(const dbx_patch_aug& a, int k, int v, const unsigned char* curves) {
@@ -116,7 +111,7 @@ template <int C, int R, class Rows>
 __host__ __device__ inline void aug_binomial(const Rows& rows, int sx, int y, int* v) {
     int cx[2 * R + 1], s[C];
 #pragma unroll
-    for (int i = 0; i <= 2 * R; ++i) cx[i] = aug_clamp(sx + i - R, 0, AUG_SIDE - 1);
+    for (int i = 0; i <= 2 * R; ++i) cx[i] = patch_clamp(sx + i - R, 0, PATCH_SIDE - 1);
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) s[ch] = 0;
 #pragma unroll
@@ -146,7 +141,7 @@ __host__ __device__ inline void aug_box(const Rows& rows, int sx, int y, int* v)
 #pragma unroll
     for (int dx = -(L / 2); dx <= L / 2; ++dx) {
         int q[C];
-        rows.template px<C>(y, aug_clamp(sx + dx, 0, AUG_SIDE - 1), q);
+        rows.template px<C>(y, patch_clamp(sx + dx, 0, PATCH_SIDE - 1), q);
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) s[ch] += q[ch];
     }
@@ -158,7 +153,7 @@ __host__ __device__ inline void aug_box(const Rows& rows, int sx, int y, int* v)
 // pixel (x, y) for x in 0..239 and y in -2..241 (replicated outside 0..239).  `a` is sanitised.
 template <int C, class Rows>
 __host__ __device__ inline void aug_gather(const Rows& rows, const dbx_patch_aug& a, int x, int y, int* v) {
-    const int sx = (a.flags & 1) ? AUG_SIDE - 1 - x : x;   // the weights are symmetric: the taps around the mirrored column
+    const int sx = (a.flags & 1) ? PATCH_SIDE - 1 - x : x;   // the weights are symmetric: the taps around the mirrored column
     switch (a.blur) {
         case 1: aug_binomial<C, 1>(rows, sx, y, v); return;
         case 2: aug_binomial<C, 2>(rows, sx, y, v); return;
@@ -200,7 +195,7 @@ struct AugHostRows {
     const unsigned char* patch;
     template <int C>
     void px(int y, int x, int* v) const {
-        const unsigned char* p = patch + ((size_t)aug_clamp(y, 0, AUG_SIDE - 1) * AUG_SIDE + x) * C;
+        const unsigned char* p = patch + ((size_t)patch_clamp(y, 0, PATCH_SIDE - 1) * PATCH_SIDE + x) * C;
         for (int ch = 0; ch < C; ++ch) v[ch] = p[ch];
     }
 };
@@ -227,30 +222,13 @@ static void aug_patch_host(const unsigned char* patch, dbx_patch_aug a, const un
     for (int k = 0; k < 3; ++k)
         for (int v = 0; v < 256; ++v) tone[256 * k + v] = (unsigned char)aug_tone(a, k, v, curves);
     const AugHostRows rows = {patch};
-    for (int y = 0; y < AUG_SIDE; ++y)
-        for (int x = 0; x < AUG_SIDE; ++x) {
+    for (int y = 0; y < PATCH_SIDE; ++y)
+        for (int x = 0; x < PATCH_SIDE; ++x) {
             int v[C];
             aug_gather<C>(rows, a, x, y, v);
-            aug_finish<C>(a, tone, y * AUG_SIDE + x, v);
-            for (int ch = 0; ch < C; ++ch) out[((size_t)y * AUG_SIDE + x) * C + ch] = (unsigned char)v[ch];
+            aug_finish<C>(a, tone, y * PATCH_SIDE + x, v);
+            for (int ch = 0; ch < C; ++ch) out[((size_t)y * PATCH_SIDE + x) * C + ch] = (unsigned char)v[ch];
         }
-}
-
-// One workgroup, slot k * AUG_THREADS + tid in pass k.
-__global__ __launch_bounds__(AUG_THREADS) void patch_aug_plan_kernel(dbx_patch_aug_io io, dbx_patch_aug_cfg cfg, int n) {
-    const int tid = threadIdx.x;
-    const bool device_mode = io.params_in == nullptr;
-    const int64_t seed = device_mode ? io.state[0] : 0, counter = device_mode ? io.state[1] : 0;
-    int cnt = *io.count;
-    cnt = cnt < 0 ? 0 : (cnt < n ? cnt : n);
-    for (int s = tid; s < cnt; s += AUG_THREADS) {
-        dbx_patch_aug a;
-        int32_t lab[12];
-        aug_plan_slot(cfg, device_mode ? nullptr : io.params_in + s, seed, counter, s, io.labels_in + 12 * s, &a, lab);
-        aug_write_slot(a, lab, s, io.params, io.labels, io.bbox, io.vertices, io.label);
-    }
-    __syncthreads();                                   // every thread has read the counter
-    if (tid == 0 && device_mode) io.state[1] = counter + 1;
 }
 
 // Workgroup t: band t % 15 (rows 16 * band .. + 15) of slot t / 15.
@@ -260,39 +238,39 @@ __global__ __launch_bounds__(AUG_THREADS) void patch_aug_plan_kernel(dbx_patch_a
 //   2. The 3 x 256 tone table, one entry per thread and colour channel.
 //   3. Pixels: thread p, p + 256, ... of the band's 3840; the bytes go to LDS at the offset the band's destination has inside a
 //      16-byte word.  The identity record copies instead.
-//   4. Stores: the band is ONE contiguous block of the output; its aligned 16-byte words, and at the two ends whole dwords, then bytes.
+//   4. Stores: patch_band_store (patch_stage.hpp).
 template <int C>
-__global__ __launch_bounds__(AUG_THREADS) void patch_augment_kernel(const unsigned char* __restrict__ src, const dbx_patch_aug* __restrict__ params,
+__global__ __launch_bounds__(PATCH_THREADS) void patch_augment_kernel(const unsigned char* __restrict__ src, const dbx_patch_aug* __restrict__ params,
                                                                     const int* __restrict__ count, const unsigned char* __restrict__ curves,
                                                                     int G, int n, unsigned char* __restrict__ dst) {
-    constexpr int RB = AUG_SIDE * C, RS = RB + 16, NR = AUG_BAND + 2 * AUG_HALO, WPR = RB / 16 + 1, NB = AUG_BAND * RB;
+    constexpr int RB = PATCH_SIDE * C, RS = RB + 16, NR = PATCH_BAND + 2 * AUG_HALO, WPR = RB / 16 + 1, NB = PATCH_BAND * RB;
     __shared__ __attribute__((aligned(16))) unsigned char in_sm[NR * RS + 16];     // + 16: the dword pair of the last pixel ends past the last row
     __shared__ __attribute__((aligned(16))) unsigned char out_sm[NB + 16];
     __shared__ unsigned char tone[3 * 256];
     const int tid = threadIdx.x;
-    const int slot = blockIdx.x / AUG_BANDS, band = blockIdx.x % AUG_BANDS;
-    const int cnt = *count;
-    if (slot >= (cnt < n ? cnt : n)) return;           // uniform over the workgroup
+    const PatchPart wg = patch_part<PATCH_BANDS>(count, n);
+    if (wg.slot >= wg.count) return;                   // uniform over the workgroup
+    const int slot = wg.slot;
     dbx_patch_aug a = params[slot];
     aug_sanitize(&a, G);
     const bool copy = aug_identity(a, C);
-    const int y0 = band * AUG_BAND;
-    const unsigned char* ps = src + (size_t)slot * AUG_SIDE * RB;
+    const int y0 = wg.part * PATCH_BAND;
+    const unsigned char* ps = src + (size_t)slot * PATCH_SIDE * RB;
     const int soff = (int)((size_t)ps & 15);
     const int vr = a.blur == 1 ? 1 : (a.blur == 2 ? 2 : 0);
-    const int w_end = (AUG_HALO + AUG_BAND + vr) * WPR;
-    for (int base = (AUG_HALO - vr) * WPR + tid; base < w_end; base += 4 * AUG_THREADS) {
+    const int w_end = (AUG_HALO + PATCH_BAND + vr) * WPR;
+    for (int base = (AUG_HALO - vr) * WPR + tid; base < w_end; base += 4 * PATCH_THREADS) {
         uint4 buf[4];                                  // four loads in flight per thread
 #pragma unroll
         for (int i = 0; i < 4; ++i) {                  // a word that is not wanted loads the row's first word instead and is not stored
-            const int w = base + i * AUG_THREADS < w_end ? base + i * AUG_THREADS : w_end - 1;
+            const int w = base + i * PATCH_THREADS < w_end ? base + i * PATCH_THREADS : w_end - 1;
             const int r = w / WPR, k = 16 * (w % WPR) < soff + RB ? w % WPR : 0;
-            const int y = aug_clamp(y0 - AUG_HALO + r, 0, AUG_SIDE - 1);
+            const int y = patch_clamp(y0 - AUG_HALO + r, 0, PATCH_SIDE - 1);
             buf[i] = reinterpret_cast<const uint4*>(ps + (size_t)y * RB - soff)[k];
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int w = base + i * AUG_THREADS, r = w / WPR, k = w % WPR;
+            const int w = base + i * PATCH_THREADS, r = w / WPR, k = w % WPR;
             if (w < w_end && 16 * k < soff + RB) reinterpret_cast<uint4*>(in_sm + r * RS)[k] = buf[i];   // the last word only when the row reaches into it
         }
     }
@@ -302,38 +280,23 @@ __global__ __launch_bounds__(AUG_THREADS) void patch_augment_kernel(const unsign
         for (int k = 0; k < K; ++k) tone[256 * k + tid] = (unsigned char)aug_tone(a, k, tid, curves);
     }
     __syncthreads();
-    unsigned char* gd = dst + ((size_t)slot * AUG_SIDE + y0) * RB;
-    const int shift = (int)((size_t)gd & 15);
+    unsigned char* gd = dst + ((size_t)slot * PATCH_SIDE + y0) * RB;
+    const int shift = patch_band_shift(gd);
     const AugLdsRows rows = {in_sm, soff, RS, y0 - AUG_HALO};
-    for (int p = tid; p < AUG_BAND * AUG_SIDE; p += AUG_THREADS) {
-        const int yy = p / AUG_SIDE, x = p % AUG_SIDE;
+    for (int p = tid; p < PATCH_BAND * PATCH_SIDE; p += PATCH_THREADS) {
+        const int yy = p / PATCH_SIDE, x = p % PATCH_SIDE;
         int v[C];
         if (copy) {
             rows.template px<C>(y0 + yy, x, v);
         } else {
             aug_gather<C>(rows, a, x, y0 + yy, v);
-            aug_finish<C>(a, tone, (y0 + yy) * AUG_SIDE + x, v);
+            aug_finish<C>(a, tone, (y0 + yy) * PATCH_SIDE + x, v);
         }
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) out_sm[shift + p * C + ch] = (unsigned char)v[ch];
     }
     __syncthreads();
-    const int end = shift + NB;
-    unsigned char* gw = gd - shift;                    // 16-byte aligned; byte b of the band is gw[shift + b] = out_sm[shift + b]
-    for (int k = tid; 16 * k < end; k += AUG_THREADS) {
-        const int b0 = 16 * k;
-        if (b0 >= shift && b0 + 16 <= end) {
-            reinterpret_cast<uint4*>(gw)[k] = reinterpret_cast<const uint4*>(out_sm)[k];
-        } else {
-            for (int j = b0; j < b0 + 16; j += 4) {
-                if (j >= shift && j + 4 <= end) {
-                    reinterpret_cast<unsigned int*>(gw)[j >> 2] = reinterpret_cast<const unsigned int*>(out_sm)[j >> 2];
-                } else {
-                    for (int q = j < shift ? shift : j; q < j + 4 && q < end; ++q) gw[q] = out_sm[q];
-                }
-            }
-        }
-    }
+    patch_band_store<NB>(out_sm, gd, tid);
 }
 
 static int aug_check_cfg(const char* who, const dbx_patch_aug_cfg* f) {
@@ -365,38 +328,29 @@ static int aug_check_cfg(const char* who, const dbx_patch_aug_cfg* f) {
 extern "C" int dbx_patch_aug_plan(const dbx_patch_aug_io* io, const dbx_patch_aug_cfg* cfg, int32_t n, void* stream) {
     DBX_REQUIRE(io, "patch_aug_plan: null io");
     if (int rc = aug_check_cfg("patch_aug_plan", cfg)) return rc;
-    DBX_REQUIRE(n >= 1 && n <= AUG_MAX_N, "patch_aug_plan: n=%d must be 1..%d", n, AUG_MAX_N);
+    DBX_REQUIRE(n >= 1 && n <= PATCH_MAX_N, "patch_aug_plan: n=%d must be 1..%d", n, PATCH_MAX_N);
     DBX_REQUIRE(io->labels_in && io->count, "patch_aug_plan: null input");
     DBX_REQUIRE(io->params_in || io->state, "patch_aug_plan: null state in device mode");
     DBX_REQUIRE(io->params && io->labels && io->bbox && io->vertices && io->label, "patch_aug_plan: null output");
-    hipLaunchKernelGGL(patch_aug_plan_kernel, dim3(1), dim3(AUG_THREADS), 0, (hipStream_t)stream, *io, *cfg, n);
+    hipLaunchKernelGGL(patch_stage_plan_kernel<AugStage>, dim3(1), dim3(PATCH_THREADS), 0, (hipStream_t)stream, *io, *cfg, n);
     DBX_LAUNCH_CHECK();
     return DBX_OK;
 }
 
 static int aug_check_pixels(const char* who, const void* patches, const void* params, const void* curves, int G, int c, const void* out,
                             long long n) {
-    DBX_REQUIRE(c >= 1 && c <= 4, "%s: c=%d must be 1..4", who, c);
     DBX_REQUIRE(G >= 0 && G <= AUG_MAX_G, "%s: G=%d must be 0..%d", who, G, AUG_MAX_G);
-    DBX_REQUIRE(patches && params && out && (curves || G == 0), "%s: null argument", who);
-    const uintptr_t a = (uintptr_t)patches, b = (uintptr_t)out, bytes = (uintptr_t)(n * AUG_SIDE * AUG_SIDE * c);
-    DBX_REQUIRE((a >= b ? a - b : b - a) >= bytes, "%s: patches and out overlap (out of place only: a blurred band reads its neighbours' rows)",
-                who);
-    return DBX_OK;
+    DBX_REQUIRE(params && (curves || G == 0), "%s: null argument", who);
+    return patch_check_pixels(who, patches, out, c, n, "a blurred band reads its neighbours' rows");
 }
 
 extern "C" int dbx_patch_augment(const uint8_t* patches, const dbx_patch_aug* params, const int32_t* count, const uint8_t* curves, int32_t G,
                                  int32_t n, int32_t c, uint8_t* out, void* stream) {
-    DBX_REQUIRE(n >= 1 && n <= AUG_MAX_N, "patch_augment: n=%d must be 1..%d", n, AUG_MAX_N);
+    DBX_REQUIRE(n >= 1 && n <= PATCH_MAX_N, "patch_augment: n=%d must be 1..%d", n, PATCH_MAX_N);
     if (int rc = aug_check_pixels("patch_augment", patches, params, curves, G, c, out, n)) return rc;
     DBX_REQUIRE(count, "patch_augment: null count");
-    const dim3 grid((unsigned)n * AUG_BANDS), block(AUG_THREADS);
-    switch (c) {
-        case 1: hipLaunchKernelGGL(patch_augment_kernel<1>, grid, block, 0, (hipStream_t)stream, patches, params, count, curves, G, n, out); break;
-        case 2: hipLaunchKernelGGL(patch_augment_kernel<2>, grid, block, 0, (hipStream_t)stream, patches, params, count, curves, G, n, out); break;
-        case 3: hipLaunchKernelGGL(patch_augment_kernel<3>, grid, block, 0, (hipStream_t)stream, patches, params, count, curves, G, n, out); break;
-        default: hipLaunchKernelGGL(patch_augment_kernel<4>, grid, block, 0, (hipStream_t)stream, patches, params, count, curves, G, n, out); break;
-    }
+    const dim3 grid((unsigned)n * PATCH_BANDS), block(PATCH_THREADS);
+    PATCH_WITH_C(c, hipLaunchKernelGGL(patch_augment_kernel<C>, grid, block, 0, (hipStream_t)stream, patches, params, count, curves, G, n, out));
     DBX_LAUNCH_CHECK();
     return DBX_OK;
 }
@@ -405,25 +359,15 @@ extern "C" int dbx_patch_aug_params_host(const dbx_patch_aug_cfg* cfg, int64_t s
                                          const int32_t* labels_in, int32_t count, dbx_patch_aug* params, int32_t* labels, float* bbox,
                                          float* vertices, float* label) {
     if (int rc = aug_check_cfg("patch_aug_params_host", cfg)) return rc;
-    DBX_REQUIRE(count >= 0 && count <= AUG_MAX_N, "patch_aug_params_host: count=%d must be 0..%d", count, AUG_MAX_N);
+    DBX_REQUIRE(count >= 0 && count <= PATCH_MAX_N, "patch_aug_params_host: count=%d must be 0..%d", count, PATCH_MAX_N);
     DBX_REQUIRE(count == 0 || (labels_in && params && labels && bbox && vertices && label), "patch_aug_params_host: null argument");
-    for (int s = 0; s < count; ++s) {
-        dbx_patch_aug a;
-        int32_t lab[12];
-        aug_plan_slot(*cfg, params_in ? params_in + s : nullptr, seed, counter, s, labels_in + 12 * s, &a, lab);
-        aug_write_slot(a, lab, s, params, labels, bbox, vertices, label);
-    }
+    patch_stage_plan_host<AugStage>({labels_in, nullptr, params_in, nullptr, params, labels, bbox, vertices, label}, *cfg, seed, counter, count);
     return DBX_OK;
 }
 
 extern "C" int dbx_patch_augment_host(const uint8_t* patch, const dbx_patch_aug* rec, const uint8_t* curves, int32_t G, int32_t c,
                                       uint8_t* out) {
     if (int rc = aug_check_pixels("patch_augment_host", patch, rec, curves, G, c, out, 1)) return rc;
-    switch (c) {
-        case 1: aug_patch_host<1>(patch, *rec, curves, G, out); break;
-        case 2: aug_patch_host<2>(patch, *rec, curves, G, out); break;
-        case 3: aug_patch_host<3>(patch, *rec, curves, G, out); break;
-        default: aug_patch_host<4>(patch, *rec, curves, G, out); break;
-    }
+    PATCH_WITH_C(c, aug_patch_host<C>(patch, *rec, curves, G, out));
     return DBX_OK;
 }

@@ -11,6 +11,7 @@
 #pragma clang fp contract(off)
 #include "common.hpp"
 #include "patch_hash.hpp"
+#include "patch_stage.hpp"
 #include "resize_tile.hpp"
 
 #include <math.h>
@@ -21,7 +22,6 @@ static_assert(offsetof(dbx_patch_job, row_bytes) == offsetof(ResizeJobDev, row_b
               offsetof(dbx_patch_job, frame) == offsetof(ResizeJobDev, pad), "dbx_patch_job layout");
 static_assert(sizeof(dbx_patch_geom) == 72 && sizeof(dbx_patch_plan_io) == 136, "patch ABI layouts");
 
-#define PATCH_THREADS 256
 #define PATCH_TILES_X ((DBX_PATCH_SIDE + RSZ_TW - 1) / RSZ_TW)
 #define PATCH_TILES (PATCH_TILES_X * ((DBX_PATCH_SIDE + RSZ_TH - 1) / RSZ_TH))
 
@@ -216,10 +216,7 @@ __global__ __launch_bounds__(PATCH_THREADS) void patch_plan_kernel(dbx_patch_pla
                 J.pad_l = 0; J.pad_t = 0; J.vw = J.cw; J.vh = J.ch; J.dh = DBX_PATCH_SIDE; J.dw = DBX_PATCH_SIDE; J.pad_value = 0;
                 J.tiles_x = PATCH_TILES_X; J.frame = frame; J.kind = kind; J.reserved = 0;
                 io.jobs[rank] = J;
-                for (int k = 0; k < 12; ++k) io.labels[12 * rank + k] = g.labels[k];
-                for (int k = 0; k < 4; ++k) io.bbox[4 * rank + k] = (float)((double)g.labels[k] / 4.0);
-                for (int k = 0; k < 8; ++k) io.vertices[8 * rank + k] = (float)((double)g.labels[4 + k] / 4.0);
-                io.label[rank] = kind ? 0.0f : 1.0f;
+                patch_write_labels(g.labels, rank, io.labels, io.bbox, io.vertices, io.label, kind != 0);
             }
         }
         __syncthreads();                               // wave_total is rewritten by the next pass
@@ -235,9 +232,9 @@ __global__ __launch_bounds__(PATCH_THREADS) void patch_plan_kernel(dbx_patch_pla
 template <int C>
 __global__ __launch_bounds__(RSZ_THREADS) void patch_cut_kernel(const ResizeJobDev* __restrict__ jobs, const int* __restrict__ count, int n,
                                                                 unsigned char* __restrict__ patches) {
-    const int slot = blockIdx.x / PATCH_TILES, tt = blockIdx.x % PATCH_TILES;
-    const int cnt = *count;
-    if (slot >= (cnt < n ? cnt : n)) return;           // uniform over the workgroup
+    const PatchPart wg = patch_part<PATCH_TILES>(count, n);
+    if (wg.slot >= wg.count) return;                   // uniform over the workgroup
+    const int slot = wg.slot, tt = wg.part;
     const int x0 = (tt % PATCH_TILES_X) * RSZ_TW, y0 = (tt / PATCH_TILES_X) * RSZ_TH;
     resize_tile_body(jobs + slot, patches + (size_t)slot * DBX_PATCH_SIDE * DBX_PATCH_SIDE * C, x0, y0, RszSrcU8<C>(jobs + slot));
 }
@@ -271,12 +268,7 @@ extern "C" int dbx_patch_cut(const dbx_patch_job* jobs, const int32_t* count, in
     DBX_REQUIRE(jobs && count && patches, "patch_cut: null argument");
     const ResizeJobDev* dj = (const ResizeJobDev*)jobs;
     const dim3 grid((unsigned)n * PATCH_TILES), block(RSZ_THREADS);
-    switch (c) {
-        case 1: hipLaunchKernelGGL(patch_cut_kernel<1>, grid, block, 0, (hipStream_t)stream, dj, count, n, patches); break;
-        case 2: hipLaunchKernelGGL(patch_cut_kernel<2>, grid, block, 0, (hipStream_t)stream, dj, count, n, patches); break;
-        case 3: hipLaunchKernelGGL(patch_cut_kernel<3>, grid, block, 0, (hipStream_t)stream, dj, count, n, patches); break;
-        default: hipLaunchKernelGGL(patch_cut_kernel<4>, grid, block, 0, (hipStream_t)stream, dj, count, n, patches); break;
-    }
+    PATCH_WITH_C(c, hipLaunchKernelGGL(patch_cut_kernel<C>, grid, block, 0, (hipStream_t)stream, dj, count, n, patches));
     DBX_LAUNCH_CHECK();
     return DBX_OK;
 }

@@ -6,35 +6,26 @@
 #pragma clang fp contract(off)
 #include "common.hpp"
 #include "patch_hash.hpp"
+#include "patch_stage.hpp"
 #include "warp_px.hpp"
 
 static_assert(sizeof(dbx_patch_warp_rec) == 64 && sizeof(dbx_patch_warp_cfg) == 72 && sizeof(dbx_patch_warp_io) == 96, "warp ABI layouts");
 static_assert(offsetof(dbx_patch_warp_rec, quad) == 16 && offsetof(dbx_patch_warp_rec, scale) == 48 && offsetof(dbx_patch_warp_cfg, rot_lo) == 8 &&
               offsetof(dbx_patch_warp_cfg, tx) == 40 && offsetof(dbx_patch_warp_cfg, R) == 64, "warp ABI layouts");
 
-#define WARP_THREADS 256
-#define WARP_SIDE DBX_PATCH_SIDE
-#define WARP_BAND 16
-#define WARP_BANDS (WARP_SIDE / WARP_BAND)
-#define WARP_MAX_N 4096
 #define WARP_MAX_R 65536
 #define WARP_QUAD_MAX (1 << 20)
 #define WARP_HALF 1912                                 // 119.5 pixels in 1/16 pixel
-#define WARP_FULL (16 * (WARP_SIDE - 1))
+#define WARP_FULL (16 * (PATCH_SIDE - 1))
 
-__host__ __device__ inline int warp_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __host__ __device__ inline bool warp_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }     // false for NaN
 
 // what a kernel reads of a record
 __host__ __device__ inline void warp_sanitize(dbx_patch_warp_rec* r) {
     r->flags &= 1;
     if (r->border < 0 || r->border > 1) r->border = 0;
-    for (int k = 0; k < 8; ++k) r->quad[k] = warp_clamp(r->quad[k], -WARP_QUAD_MAX, WARP_QUAD_MAX);
+    for (int k = 0; k < 8; ++k) r->quad[k] = patch_clamp(r->quad[k], -WARP_QUAD_MAX, WARP_QUAD_MAX);
     r->reserved = 0;
-}
-
-__host__ __device__ inline int warp_range(uint64_t h, int lo, int hi) {
-    return (int)((int64_t)lo + (int64_t)((h >> 11) % (uint64_t)((int64_t)hi - (int64_t)lo + 1)));
 }
 
 // the record of slot s in device mode: a fixed draw number per field
@@ -44,15 +35,15 @@ __host__ __device__ inline void warp_draw(const dbx_patch_warp_cfg& f, const int
     r->flags = on ? 1 : 0;
     r->border = f.border;
     r->fill = f.fill;
-    r->rot = warp_range(patch_hash(seed, counter, s, 1), f.rot_lo, f.rot_hi);
-    r->scale = warp_range(patch_hash(seed, counter, s, 2), f.scale_lo, f.scale_hi);
-    r->aspect = warp_range(patch_hash(seed, counter, s, 3), f.aspect_lo, f.aspect_hi);
-    r->shear = warp_range(patch_hash(seed, counter, s, 4), f.shear_lo, f.shear_hi);
+    r->rot = patch_range(patch_hash(seed, counter, s, 1), f.rot_lo, f.rot_hi);
+    r->scale = patch_range(patch_hash(seed, counter, s, 2), f.scale_lo, f.scale_hi);
+    r->aspect = patch_range(patch_hash(seed, counter, s, 3), f.aspect_lo, f.aspect_hi);
+    r->shear = patch_range(patch_hash(seed, counter, s, 4), f.shear_lo, f.shear_hi);
     r->reserved = 0;
     const int ident[8] = {0, 0, WARP_FULL, 0, WARP_FULL, WARP_FULL, 0, WARP_FULL};
     for (int k = 0; k < 8; ++k) r->quad[k] = ident[k];
     if (!on) return;                                   // the bank is not read
-    const int64_t t[2] = {warp_range(patch_hash(seed, counter, s, 5), -f.tx, f.tx), warp_range(patch_hash(seed, counter, s, 6), -f.ty, f.ty)};
+    const int64_t t[2] = {patch_range(patch_hash(seed, counter, s, 5), -f.tx, f.tx), patch_range(patch_hash(seed, counter, s, 6), -f.ty, f.ty)};
     const int64_t co = bank[2 * r->rot], si = bank[2 * r->rot + 1];
     const int64_t sc = r->scale, as = r->aspect, sh = r->shear;
     for (int k = 0; k < 4; ++k) {
@@ -62,7 +53,7 @@ __host__ __device__ inline void warp_draw(const dbx_patch_warp_cfg& f, const int
         u += (sh * v) >> 8;
         const int64_t xy[2] = {(co * u - si * v + 32768) >> 16, (si * u + co * v + 32768) >> 16};
         for (int a = 0; a < 2; ++a) {
-            const int64_t q = xy[a] + WARP_HALF + t[a] + warp_range(patch_hash(seed, counter, s, 7 + 2 * k + a), -f.jitter, f.jitter);
+            const int64_t q = xy[a] + WARP_HALF + t[a] + patch_range(patch_hash(seed, counter, s, 7 + 2 * k + a), -f.jitter, f.jitter);
             r->quad[2 * k + a] = (int)(q < -WARP_QUAD_MAX ? -WARP_QUAD_MAX : (q > WARP_QUAD_MAX ? WARP_QUAD_MAX : q));
         }
     }
@@ -73,9 +64,9 @@ __host__ __device__ inline bool warp_vertex(const double* m, int vx, int vy, int
     const double W = m[6] * vx + m[7] * vy + m[8];
     if (!warp_finite(W) || !(W > 0.0)) return false;
     const double fx = (m[0] * vx + m[1] * vy + m[2]) / W + 0.5, fy = (m[3] * vx + m[4] * vy + m[5]) / W + 0.5;
-    if (!(fx > -1.0 && fx < (double)WARP_SIDE && fy > -1.0 && fy < (double)WARP_SIDE)) return false;   // also NaN; the casts below are defined
+    if (!(fx > -1.0 && fx < (double)PATCH_SIDE && fy > -1.0 && fy < (double)PATCH_SIDE)) return false;   // also NaN; the casts below are defined
     const int x = (int)fx, y = (int)fy;
-    if (x < margin || x > WARP_SIDE - 1 - margin || y < margin || y > WARP_SIDE - 1 - margin) return false;
+    if (x < margin || x > PATCH_SIDE - 1 - margin || y < margin || y > PATCH_SIDE - 1 - margin) return false;
     *ox = x; *oy = y;
     return true;
 }
@@ -87,11 +78,11 @@ __host__ __device__ inline void warp_plan_slot(const dbx_patch_warp_cfg& f, cons
     if (injected) *r = *injected;
     else warp_draw(f, bank, seed, counter, s, r);
     warp_sanitize(r);
-    bool negative = true;
-    for (int k = 0; k < 12; ++k) { lout[k] = lin[k]; negative = negative && lin[k] == 0; }
+    const bool negative = patch_row_negative(lin);
+    for (int k = 0; k < 12; ++k) lout[k] = lin[k];
     for (int k = 0; k < 9; ++k) fwd[k] = inv[k] = (k % 4 == 0) ? 1.0 : 0.0;
     if (!(r->flags & 1)) return;
-    const double e = (double)(WARP_SIDE - 1);
+    const double e = (double)(PATCH_SIDE - 1);
     const double sq[8] = {0.0, 0.0, e, 0.0, e, e, 0.0, e};
     double d[8], m[9], im[9];
     for (int k = 0; k < 8; ++k) d[k] = (double)r->quad[k] / 16.0;
@@ -117,106 +108,76 @@ __host__ __device__ inline void warp_plan_slot(const dbx_patch_warp_cfg& f, cons
     for (int k = 0; k < 9; ++k) { fwd[k] = m[k]; inv[k] = im[k]; }
 }
 
-__host__ __device__ inline void warp_write_slot(const dbx_patch_warp_rec& r, const int32_t* lab, const double* fwd, const double* inv, int s,
-                                                dbx_patch_warp_rec* params, int32_t* labels, float* bbox, float* vertices, float* label,
-                                                double* fwd_out, double* inv_out) {
-    params[s] = r;
-    bool negative = true;
-    for (int k = 0; k < 12; ++k) { labels[12 * s + k] = lab[k]; negative = negative && lab[k] == 0; }
-    for (int k = 0; k < 4; ++k) bbox[4 * s + k] = (float)((double)lab[k] / 4.0);
-    for (int k = 0; k < 8; ++k) vertices[8 * s + k] = (float)((double)lab[4 + k] / 4.0);
-    label[s] = negative ? 0.0f : 1.0f;
-    for (int k = 0; k < 9; ++k) { fwd_out[9 * s + k] = fwd[k]; inv_out[9 * s + k] = inv[k]; }
-}
+// patch_stage.hpp's policy: the plan kernel and its host loop over warp_plan_slot
+struct WarpStage {
+    typedef dbx_patch_warp_io io_t;
+    typedef dbx_patch_warp_cfg cfg_t;
+    __host__ __device__ static void slot(const io_t& io, const cfg_t& f, bool device_mode, int64_t seed, int64_t counter, int s) {
+        dbx_patch_warp_rec r;
+        int32_t lab[12];
+        double fwd[9], inv[9];
+        warp_plan_slot(f, device_mode ? nullptr : io.params_in + s, io.rot, seed, counter, s, io.labels_in + 12 * s, &r, lab, fwd, inv);
+        io.params[s] = r;
+        patch_write_labels(lab, s, io.labels, io.bbox, io.vertices, io.label, patch_row_negative(lab));
+        for (int k = 0; k < 9; ++k) { io.fwd[9 * s + k] = fwd[k]; io.inv[9 * s + k] = inv[k]; }
+    }
+};
 
 // the C channels of output pixel (x, y) of a slot, channel ch in byte ch; r is sanitised
 template <int C>
 __host__ __device__ inline unsigned int warp_pixel(const unsigned char* patch, const dbx_patch_warp_rec& r, const double* im, int x, int y) {
     if (!(r.flags & 1)) {
         unsigned int px = 0;
-        for (int ch = 0; ch < C; ++ch) px |= (unsigned int)patch[((size_t)y * WARP_SIDE + x) * C + ch] << (8 * ch);
+        for (int ch = 0; ch < C; ++ch) px |= (unsigned int)patch[((size_t)y * PATCH_SIDE + x) * C + ch] << (8 * ch);
         return px;
     }
-    if (r.border) return warp_px_u8_border<1>(im, patch, WARP_SIDE, WARP_SIDE, C, x, y, 0u);
-    return warp_px_u8_border<0>(im, patch, WARP_SIDE, WARP_SIDE, C, x, y, (unsigned int)r.fill);
+    if (r.border) return warp_px_u8_border<1>(im, patch, PATCH_SIDE, PATCH_SIDE, C, x, y, 0u);
+    return warp_px_u8_border<0>(im, patch, PATCH_SIDE, PATCH_SIDE, C, x, y, (unsigned int)r.fill);
 }
 
 template <int C>
 static void warp_patch_host(const unsigned char* patch, dbx_patch_warp_rec r, const double* im, unsigned char* out) {
     warp_sanitize(&r);
-    for (int y = 0; y < WARP_SIDE; ++y)
-        for (int x = 0; x < WARP_SIDE; ++x) {
+    for (int y = 0; y < PATCH_SIDE; ++y)
+        for (int x = 0; x < PATCH_SIDE; ++x) {
             const unsigned int px = warp_pixel<C>(patch, r, im, x, y);
-            for (int ch = 0; ch < C; ++ch) out[((size_t)y * WARP_SIDE + x) * C + ch] = (unsigned char)(px >> (8 * ch));
+            for (int ch = 0; ch < C; ++ch) out[((size_t)y * PATCH_SIDE + x) * C + ch] = (unsigned char)(px >> (8 * ch));
         }
-}
-
-// One workgroup, slot k * WARP_THREADS + tid in pass k.
-__global__ __launch_bounds__(WARP_THREADS) void patch_warp_plan_kernel(dbx_patch_warp_io io, dbx_patch_warp_cfg cfg, int n) {
-    const int tid = threadIdx.x;
-    const bool device_mode = io.params_in == nullptr;
-    const int64_t seed = device_mode ? io.state[0] : 0, counter = device_mode ? io.state[1] : 0;
-    int cnt = *io.count;
-    cnt = cnt < 0 ? 0 : (cnt < n ? cnt : n);
-    for (int s = tid; s < cnt; s += WARP_THREADS) {
-        dbx_patch_warp_rec r;
-        int32_t lab[12];
-        double fwd[9], inv[9];
-        warp_plan_slot(cfg, device_mode ? nullptr : io.params_in + s, io.rot, seed, counter, s, io.labels_in + 12 * s, &r, lab, fwd, inv);
-        warp_write_slot(r, lab, fwd, inv, s, io.params, io.labels, io.bbox, io.vertices, io.label, io.fwd, io.inv);
-    }
-    __syncthreads();                                   // every thread has read the counter
-    if (tid == 0 && device_mode) io.state[1] = counter + 1;
 }
 
 // Workgroup t: band t % 15 (rows 16 * band .. + 15) of slot t / 15.
 //   1. Pixels: thread p, p + 256, ... of the band's 3840, so the lanes of a wave make 64 CONSECUTIVE output pixels and their gathers
 //      cover a narrow span of the source patch, which is read in place (a batch of patches is cache resident).  The bytes go to LDS at
 //      the offset the band's destination has inside a 16-byte word.  A slot with bit 0 clear copies instead.
-//   2. Stores: the band is ONE contiguous block of the output; its aligned 16-byte words, and at the two ends whole dwords, then bytes.
+//   2. Stores: patch_band_store (patch_stage.hpp).
 // Whatever inv holds, warp_px_u8_border reads inside the slot's 240 x 240 patch only.
 template <int C>
-__global__ __launch_bounds__(WARP_THREADS) void patch_warp_kernel(const unsigned char* __restrict__ src, const dbx_patch_warp_rec* __restrict__ params,
+__global__ __launch_bounds__(PATCH_THREADS) void patch_warp_kernel(const unsigned char* __restrict__ src, const dbx_patch_warp_rec* __restrict__ params,
                                                                   const double* __restrict__ inv, const int* __restrict__ count, int n,
                                                                   unsigned char* __restrict__ dst) {
-    constexpr int RB = WARP_SIDE * C, NB = WARP_BAND * RB;
+    constexpr int RB = PATCH_SIDE * C, NB = PATCH_BAND * RB;
     __shared__ __attribute__((aligned(16))) unsigned char out_sm[NB + 16];
     const int tid = threadIdx.x;
-    const int slot = blockIdx.x / WARP_BANDS, band = blockIdx.x % WARP_BANDS;
-    const int cnt = *count;
-    if (slot >= (cnt < n ? cnt : n)) return;           // uniform over the workgroup
+    const PatchPart wg = patch_part<PATCH_BANDS>(count, n);
+    if (wg.slot >= wg.count) return;                   // uniform over the workgroup
+    const int slot = wg.slot;
     dbx_patch_warp_rec r = params[slot];
     warp_sanitize(&r);
     double im[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) im[k] = inv[9 * (size_t)slot + k];
-    const int y0 = band * WARP_BAND;
-    const unsigned char* ps = src + (size_t)slot * WARP_SIDE * RB;
-    unsigned char* gd = dst + ((size_t)slot * WARP_SIDE + y0) * RB;
-    const int shift = (int)((size_t)gd & 15);
-    for (int p = tid; p < WARP_BAND * WARP_SIDE; p += WARP_THREADS) {
-        const int yy = p / WARP_SIDE, x = p % WARP_SIDE;
+    const int y0 = wg.part * PATCH_BAND;
+    const unsigned char* ps = src + (size_t)slot * PATCH_SIDE * RB;
+    unsigned char* gd = dst + ((size_t)slot * PATCH_SIDE + y0) * RB;
+    const int shift = patch_band_shift(gd);
+    for (int p = tid; p < PATCH_BAND * PATCH_SIDE; p += PATCH_THREADS) {
+        const int yy = p / PATCH_SIDE, x = p % PATCH_SIDE;
         const unsigned int px = warp_pixel<C>(ps, r, im, x, y0 + yy);
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) out_sm[shift + p * C + ch] = (unsigned char)(px >> (8 * ch));
     }
     __syncthreads();
-    const int end = shift + NB;
-    unsigned char* gw = gd - shift;                    // 16-byte aligned; byte b of the band is gw[shift + b] = out_sm[shift + b]
-    for (int k = tid; 16 * k < end; k += WARP_THREADS) {
-        const int b0 = 16 * k;
-        if (b0 >= shift && b0 + 16 <= end) {
-            reinterpret_cast<uint4*>(gw)[k] = reinterpret_cast<const uint4*>(out_sm)[k];
-        } else {
-            for (int j = b0; j < b0 + 16; j += 4) {
-                if (j >= shift && j + 4 <= end) {
-                    reinterpret_cast<unsigned int*>(gw)[j >> 2] = reinterpret_cast<const unsigned int*>(out_sm)[j >> 2];
-                } else {
-                    for (int q = j < shift ? shift : j; q < j + 4 && q < end; ++q) gw[q] = out_sm[q];
-                }
-            }
-        }
-    }
+    patch_band_store<NB>(out_sm, gd, tid);
 }
 
 static int warp_check_cfg(const char* who, const dbx_patch_warp_cfg* f, bool device_mode, const void* bank) {
@@ -246,35 +207,27 @@ static int warp_check_cfg(const char* who, const dbx_patch_warp_cfg* f, bool dev
 extern "C" int dbx_patch_warp_plan(const dbx_patch_warp_io* io, const dbx_patch_warp_cfg* cfg, int32_t n, void* stream) {
     DBX_REQUIRE(io, "patch_warp_plan: null io");
     if (int rc = warp_check_cfg("patch_warp_plan", cfg, io->params_in == nullptr, io->rot)) return rc;
-    DBX_REQUIRE(n >= 1 && n <= WARP_MAX_N, "patch_warp_plan: n=%d must be 1..%d", n, WARP_MAX_N);
+    DBX_REQUIRE(n >= 1 && n <= PATCH_MAX_N, "patch_warp_plan: n=%d must be 1..%d", n, PATCH_MAX_N);
     DBX_REQUIRE(io->labels_in && io->count, "patch_warp_plan: null input");
     DBX_REQUIRE(io->params_in || io->state, "patch_warp_plan: null state in device mode");
     DBX_REQUIRE(io->params && io->labels && io->bbox && io->vertices && io->label && io->fwd && io->inv, "patch_warp_plan: null output");
-    hipLaunchKernelGGL(patch_warp_plan_kernel, dim3(1), dim3(WARP_THREADS), 0, (hipStream_t)stream, *io, *cfg, n);
+    hipLaunchKernelGGL(patch_stage_plan_kernel<WarpStage>, dim3(1), dim3(PATCH_THREADS), 0, (hipStream_t)stream, *io, *cfg, n);
     DBX_LAUNCH_CHECK();
     return DBX_OK;
 }
 
 static int warp_check_pixels(const char* who, const void* patches, const void* params, const void* inv, int c, const void* out, long long n) {
-    DBX_REQUIRE(c >= 1 && c <= 4, "%s: c=%d must be 1..4", who, c);
-    DBX_REQUIRE(patches && params && inv && out, "%s: null argument", who);
-    const uintptr_t a = (uintptr_t)patches, b = (uintptr_t)out, bytes = (uintptr_t)(n * WARP_SIDE * WARP_SIDE * c);
-    DBX_REQUIRE((a >= b ? a - b : b - a) >= bytes, "%s: patches and out overlap (out of place only: a warped pixel reads anywhere in its patch)", who);
-    return DBX_OK;
+    DBX_REQUIRE(params && inv, "%s: null argument", who);
+    return patch_check_pixels(who, patches, out, c, n, "a warped pixel reads anywhere in its patch");
 }
 
 extern "C" int dbx_patch_warp(const uint8_t* patches, const dbx_patch_warp_rec* params, const double* inv, const int32_t* count, int32_t n,
                               int32_t c, uint8_t* out, void* stream) {
-    DBX_REQUIRE(n >= 1 && n <= WARP_MAX_N, "patch_warp: n=%d must be 1..%d", n, WARP_MAX_N);
+    DBX_REQUIRE(n >= 1 && n <= PATCH_MAX_N, "patch_warp: n=%d must be 1..%d", n, PATCH_MAX_N);
     if (int rc = warp_check_pixels("patch_warp", patches, params, inv, c, out, n)) return rc;
     DBX_REQUIRE(count, "patch_warp: null count");
-    const dim3 grid((unsigned)n * WARP_BANDS), block(WARP_THREADS);
-    switch (c) {
-        case 1: hipLaunchKernelGGL(patch_warp_kernel<1>, grid, block, 0, (hipStream_t)stream, patches, params, inv, count, n, out); break;
-        case 2: hipLaunchKernelGGL(patch_warp_kernel<2>, grid, block, 0, (hipStream_t)stream, patches, params, inv, count, n, out); break;
-        case 3: hipLaunchKernelGGL(patch_warp_kernel<3>, grid, block, 0, (hipStream_t)stream, patches, params, inv, count, n, out); break;
-        default: hipLaunchKernelGGL(patch_warp_kernel<4>, grid, block, 0, (hipStream_t)stream, patches, params, inv, count, n, out); break;
-    }
+    const dim3 grid((unsigned)n * PATCH_BANDS), block(PATCH_THREADS);
+    PATCH_WITH_C(c, hipLaunchKernelGGL(patch_warp_kernel<C>, grid, block, 0, (hipStream_t)stream, patches, params, inv, count, n, out));
     DBX_LAUNCH_CHECK();
     return DBX_OK;
 }
@@ -283,25 +236,15 @@ extern "C" int dbx_patch_warp_params_host(const dbx_patch_warp_cfg* cfg, int64_t
                                           const int32_t* rot, const int32_t* labels_in, int32_t count, dbx_patch_warp_rec* params,
                                           int32_t* labels, float* bbox, float* vertices, float* label, double* fwd, double* inv) {
     if (int rc = warp_check_cfg("patch_warp_params_host", cfg, params_in == nullptr, rot)) return rc;
-    DBX_REQUIRE(count >= 0 && count <= WARP_MAX_N, "patch_warp_params_host: count=%d must be 0..%d", count, WARP_MAX_N);
+    DBX_REQUIRE(count >= 0 && count <= PATCH_MAX_N, "patch_warp_params_host: count=%d must be 0..%d", count, PATCH_MAX_N);
     DBX_REQUIRE(count == 0 || (labels_in && params && labels && bbox && vertices && label && fwd && inv), "patch_warp_params_host: null argument");
-    for (int s = 0; s < count; ++s) {
-        dbx_patch_warp_rec r;
-        int32_t lab[12];
-        double m[9], im[9];
-        warp_plan_slot(*cfg, params_in ? params_in + s : nullptr, rot, seed, counter, s, labels_in + 12 * s, &r, lab, m, im);
-        warp_write_slot(r, lab, m, im, s, params, labels, bbox, vertices, label, fwd, inv);
-    }
+    patch_stage_plan_host<WarpStage>({labels_in, nullptr, params_in, nullptr, rot, params, labels, bbox, vertices, label, fwd, inv}, *cfg, seed, counter,
+                                     count);
     return DBX_OK;
 }
 
 extern "C" int dbx_patch_warp_host(const uint8_t* patch, const dbx_patch_warp_rec* rec, const double* inv, int32_t c, uint8_t* out) {
     if (int rc = warp_check_pixels("patch_warp_host", patch, rec, inv, c, out, 1)) return rc;
-    switch (c) {
-        case 1: warp_patch_host<1>(patch, *rec, inv, out); break;
-        case 2: warp_patch_host<2>(patch, *rec, inv, out); break;
-        case 3: warp_patch_host<3>(patch, *rec, inv, out); break;
-        default: warp_patch_host<4>(patch, *rec, inv, out); break;
-    }
+    PATCH_WITH_C(c, warp_patch_host<C>(patch, *rec, inv, out));
     return DBX_OK;
 }

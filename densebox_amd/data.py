@@ -94,17 +94,25 @@ def plate_tables(plates, n_frames):
     return rows, plate0
 
 
-class PatchPlan(object):
+class _LabelPlan(object):
+    """The zeroed label outputs every plan launch writes: labels_i32 int32 [n, 12], bbox float32 [n, 4], vertices [n, 8], labels [n, 1]."""
+
+    def __init__(self, n, device):
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+        self.n = int(n)
+        self.labels_i32, self.bbox, self.vertices, self.labels = z((n, 12), torch.int32), z((n, 4), torch.float32), z((n, 8), torch.float32), \
+            z((n, 1), torch.float32)
+
+
+class PatchPlan(_LabelPlan):
     """The device tensors one dbx_patch_plan launch writes: jobs (uint8 [n, 96], dbx_patch_job records), labels_i32 int32 [n, 12],
     bbox float32 [n, 4], vertices [n, 8], labels [n, 1], count int32 [1], tally int32 [8], status / slot int32 [M], cand int32 [M, 2],
     draws float64 [M, 2].  Rows at or past count are not written (the tensors start zeroed)."""
 
     def __init__(self, M, n, device):
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
-        self.M, self.n = int(M), int(n)
-        self.jobs = z((n, 96), torch.uint8)
-        self.labels_i32, self.bbox, self.vertices, self.labels = z((n, 12), torch.int32), z((n, 4), torch.float32), \
-            z((n, 8), torch.float32), z((n, 1), torch.float32)
+        _LabelPlan.__init__(self, n, device)
+        self.M, self.jobs = int(M), z((n, 96), torch.uint8)
         self.count, self.tally = z((1,), torch.int32), z((8,), torch.int32)
         self.status, self.slot = z((max(M, 1),), torch.int32)[:M], z((max(M, 1),), torch.int32)[:M]
         self.cand, self.draws = z((max(M, 1), 2), torch.int32)[:M], z((max(M, 1), 2), torch.float64)[:M]
@@ -195,6 +203,58 @@ def sample_patches(frames, plates, n, candidates=None, draws=None, neg_frac=0.1,
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# What the stages behind the cut share (the augmenter and the warper below; csrc/patch_stage.hpp is the device half): a plan launch
+# that decides a 64-byte record and the label row per slot, and a pixel launch of a workgroup per 16-row band.
+class _StagePlan(_LabelPlan):
+    def __init__(self, n, device):
+        _LabelPlan.__init__(self, n, device)
+        self.params = torch.zeros((n, 16), dtype=torch.int32, device=device)
+
+
+def _plan_stage(entry, io, labels_i32, count, cfg, params, state, out):
+    """The io fields every stage's plan has, then the launch `entry` on the current stream; the caller has set the stage's own fields."""
+    io.labels_in, io.count = labels_i32.data_ptr(), count.data_ptr()
+    io.params_in = params.data_ptr() if params is not None else None
+    io.state = state.data_ptr() if state is not None else None
+    io.params, io.labels, io.bbox, io.vertices, io.label = out.params.data_ptr(), out.labels_i32.data_ptr(), out.bbox.data_ptr(), \
+        out.vertices.data_ptr(), out.labels.data_ptr()
+    _lib.check(entry(C.byref(io), C.byref(cfg), int(labels_i32.size(0)), _lib.stream_ptr()))
+    return out
+
+
+def _checked_out(who, patches, out):
+    """The patches / out pair of a pixel launch, checked; returns out (a new zeroed tensor when None)."""
+    if patches.dtype != torch.uint8 or patches.dim() != 4 or tuple(patches.shape[1:3]) != (PATCH_SIDE, PATCH_SIDE) or not patches.is_contiguous():
+        raise RuntimeError('%s: patches must be a contiguous uint8 [n, 240, 240, c] tensor, got %s %s' % (who, patches.dtype, list(patches.shape)))
+    if out is None:
+        out = torch.zeros_like(patches)
+    if out.dtype != torch.uint8 or out.shape != patches.shape or not out.is_contiguous():
+        raise RuntimeError('%s: out must be a contiguous uint8 %s tensor, got %s %s' % (who, list(patches.shape), out.dtype, list(out.shape)))
+    return out
+
+
+def _stage_patches(patches, plan_or_labels, config, bank, params, counter, plan, apply, extras):
+    """augment_patches and warp_patches: one upload + the two launches.  config: the Augment or Warp (its seed); bank: its host bank,
+    flat; plan(labels_in, count, bank, params, state) and apply(patches, plan, count, bank): the stage's launches on the uploaded
+    tensors (params None in device mode); extras: the plan's tensors returned after (out, labels_i32, bbox, vertices, labels)."""
+    dev = (patches if torch.is_tensor(patches) else torch.from_numpy(np.ascontiguousarray(patches))).cuda()
+    n = int(dev.size(0))
+    parts = [bank, np.array([config.seed, counter], dtype=np.int64)]
+    if params is not None:
+        rec = params.cpu().numpy() if torch.is_tensor(params) else np.asarray(params)
+        parts.append(np.ascontiguousarray(rec.astype(np.int32).reshape(n, 16)))
+    from_plan = isinstance(plan_or_labels, PatchPlan)
+    if not from_plan:
+        rows = plan_or_labels.cpu().numpy() if torch.is_tensor(plan_or_labels) else np.asarray(plan_or_labels)
+        parts += [np.ascontiguousarray(rows.astype(np.int32).reshape(n, 12)), np.array([n], dtype=np.int32)]
+    up = _upload(*parts)
+    labels_in, count = (plan_or_labels.labels_i32, plan_or_labels.count) if from_plan else (up[-2], up[-1])
+    p = plan(labels_in, count, up[0], up[2] if params is not None else None, up[1])
+    out = apply(dev, p, count, up[0])
+    return (out, p.labels_i32, p.bbox, p.vertices, p.labels) + tuple(getattr(p, k) for k in extras)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # Photometric augmentation and horizontal flip of the cut patches on the device (dbx_patch_aug_plan + dbx_patch_augment;
 # include/densebox_hip.h, "training patch augmentation").  The reference has no augmentation: the semantics are this project's own,
 # restated in tests/aug_ref.py.
@@ -250,43 +310,24 @@ class Augment(object):
         return self._bank
 
 
-class AugPlan(object):
+class AugPlan(_StagePlan):
     """The device tensors one dbx_patch_aug_plan launch writes: params int32 [n, 16] (dbx_patch_aug records, AUG_FIELDS), labels_i32 int32
     [n, 12], bbox float32 [n, 4], vertices [n, 8], labels [n, 1].  Rows at or past the count are not written (the tensors start zeroed)."""
-
-    def __init__(self, n, device):
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
-        self.n = int(n)
-        self.params, self.labels_i32 = z((n, 16), torch.int32), z((n, 12), torch.int32)
-        self.bbox, self.vertices, self.labels = z((n, 4), torch.float32), z((n, 8), torch.float32), z((n, 1), torch.float32)
 
 
 def plan_augment(labels_i32, count, cfg, params=None, state=None, out=None):
     """The dbx_patch_aug_plan launch alone, on the current stream.  labels_i32 int32 [n, 12] and count int32 [1]: device tensors (a
     PatchPlan's); cfg: Augment.cfg(); params int32 [n, 16] (injected mode) or state int64 [2] = (seed, counter) (device mode), device
     tensors.  Returns the AugPlan (`out`, or a new one)."""
-    n = int(labels_i32.size(0))
-    out = out if out is not None else AugPlan(n, labels_i32.device)
-    io = _lib.PatchAugIO()
-    io.labels_in, io.count = labels_i32.data_ptr(), count.data_ptr()
-    io.params_in = params.data_ptr() if params is not None else None
-    io.state = state.data_ptr() if state is not None else None
-    io.params, io.labels, io.bbox, io.vertices, io.label = out.params.data_ptr(), out.labels_i32.data_ptr(), out.bbox.data_ptr(), \
-        out.vertices.data_ptr(), out.labels.data_ptr()
-    _lib.check(_lib.lib().dbx_patch_aug_plan(C.byref(io), C.byref(cfg), n, _lib.stream_ptr()))
-    return out
+    out = out if out is not None else AugPlan(labels_i32.size(0), labels_i32.device)
+    return _plan_stage(_lib.lib().dbx_patch_aug_plan, _lib.PatchAugIO(), labels_i32, count, cfg, params, state, out)
 
 
 def apply_augment(patches, params, count, curves, out=None):
     """The dbx_patch_augment launch alone: patches uint8 [n, 240, 240, c] (any byte alignment) through the records params int32 [n, 16]
     into `out` (a new zeroed tensor when None; it may not overlap patches).  curves: device uint8 [G, 256].  Slots at or past the count keep
     what they held."""
-    if patches.dtype != torch.uint8 or patches.dim() != 4 or tuple(patches.shape[1:3]) != (PATCH_SIDE, PATCH_SIDE) or not patches.is_contiguous():
-        raise RuntimeError('apply_augment: patches must be a contiguous uint8 [n, 240, 240, c] tensor, got %s %s' % (patches.dtype, list(patches.shape)))
-    if out is None:
-        out = torch.zeros_like(patches)
-    if out.dtype != torch.uint8 or out.shape != patches.shape or not out.is_contiguous():
-        raise RuntimeError('apply_augment: out must be a contiguous uint8 %s tensor, got %s %s' % (list(patches.shape), out.dtype, list(out.shape)))
+    out = _checked_out('apply_augment', patches, out)
     G = int(curves.size(0))
     _lib.check(_lib.lib().dbx_patch_augment(C.c_void_p(patches.data_ptr()), C.c_void_p(params.data_ptr()), C.c_void_p(count.data_ptr()),
                                             C.c_void_p(curves.data_ptr()) if G else None, G, int(patches.size(0)), int(patches.size(3)),
@@ -300,26 +341,10 @@ def augment_patches(patches, plan_or_labels, augment=None, params=None, counter=
     default one); params: int [n, 16] records (injected mode), else they are drawn from (augment.seed, counter).  Returns (out,
     labels_i32, bbox, vertices, labels, params): the augmented patches, the four label tensors and the records used."""
     augment = augment if augment is not None else Augment()
-    dev = patches if torch.is_tensor(patches) else torch.from_numpy(np.ascontiguousarray(patches))
-    dev = dev.cuda()
-    n = int(dev.size(0))
-    parts = [augment.curves().reshape(-1) if len(augment.gammas) else np.zeros(256, np.uint8), np.array([augment.seed, counter], dtype=np.int64)]
-    if params is not None:
-        rec = params.cpu().numpy() if torch.is_tensor(params) else np.asarray(params)
-        parts.append(np.ascontiguousarray(rec.astype(np.int32).reshape(n, 16)))
-    if isinstance(plan_or_labels, PatchPlan):
-        labels_in, count = plan_or_labels.labels_i32, plan_or_labels.count
-    else:
-        rows = plan_or_labels.cpu().numpy() if torch.is_tensor(plan_or_labels) else np.asarray(plan_or_labels)
-        parts += [np.ascontiguousarray(rows.astype(np.int32).reshape(n, 12)), np.array([n], dtype=np.int32)]
-        labels_in = count = None
-    up = _upload(*parts)
-    curves = up[0].view(-1, 256)[:len(augment.gammas)]
-    if labels_in is None:
-        labels_in, count = up[-2], up[-1]
-    plan = plan_augment(labels_in, count, augment.cfg(), params=up[2] if params is not None else None, state=up[1])
-    out = apply_augment(dev, plan.params, count, curves)
-    return out, plan.labels_i32, plan.bbox, plan.vertices, plan.labels, plan.params
+    G = len(augment.gammas)
+    return _stage_patches(patches, plan_or_labels, augment, augment.curves().reshape(-1) if G else np.zeros(256, np.uint8), params, counter,
+                          lambda rows, count, bank, rec, state: plan_augment(rows, count, augment.cfg(), params=rec, state=state),
+                          lambda dev, plan, count, bank: apply_augment(dev, plan.params, count, bank.view(-1, 256)[:G]), ('params',))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -386,47 +411,32 @@ class Warp(object):
         return self._bank
 
 
-class WarpPlan(object):
+class WarpPlan(_StagePlan):
     """The device tensors one dbx_patch_warp_plan launch writes: params int32 [n, 16] (dbx_patch_warp_rec records, WARP_FIELDS), labels_i32
     int32 [n, 12], bbox float32 [n, 4], vertices [n, 8], labels [n, 1], fwd / inv float64 [n, 9] (input -> output and output -> input;
     the exact identity for a slot that copies).  Rows at or past the count are not written (the tensors start zeroed)."""
 
     def __init__(self, n, device):
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
-        self.n = int(n)
-        self.params, self.labels_i32 = z((n, 16), torch.int32), z((n, 12), torch.int32)
-        self.bbox, self.vertices, self.labels = z((n, 4), torch.float32), z((n, 8), torch.float32), z((n, 1), torch.float32)
-        self.fwd, self.inv = z((n, 9), torch.float64), z((n, 9), torch.float64)
+        _StagePlan.__init__(self, n, device)
+        self.fwd, self.inv = torch.zeros((n, 9), dtype=torch.float64, device=device), torch.zeros((n, 9), dtype=torch.float64, device=device)
 
 
 def plan_warp(labels_i32, count, cfg, bank=None, params=None, state=None, out=None):
     """The dbx_patch_warp_plan launch alone, on the current stream.  labels_i32 int32 [n, 12] and count int32 [1]: device tensors (a
     PatchPlan's); cfg: Warp.cfg(); bank: device int32 [R, 2] (Warp.bank(), uploaded); params int32 [n, 16] (injected mode) or state int64
     [2] = (seed, counter) (device mode), device tensors.  Returns the WarpPlan (`out`, or a new one)."""
-    n = int(labels_i32.size(0))
-    out = out if out is not None else WarpPlan(n, labels_i32.device)
+    out = out if out is not None else WarpPlan(labels_i32.size(0), labels_i32.device)
     io = _lib.PatchWarpIO()
-    io.labels_in, io.count = labels_i32.data_ptr(), count.data_ptr()
-    io.params_in = params.data_ptr() if params is not None else None
-    io.state = state.data_ptr() if state is not None else None
     io.rot = bank.data_ptr() if bank is not None and bank.numel() else None
-    io.params, io.labels, io.bbox, io.vertices, io.label = out.params.data_ptr(), out.labels_i32.data_ptr(), out.bbox.data_ptr(), \
-        out.vertices.data_ptr(), out.labels.data_ptr()
     io.fwd, io.inv = out.fwd.data_ptr(), out.inv.data_ptr()
-    _lib.check(_lib.lib().dbx_patch_warp_plan(C.byref(io), C.byref(cfg), n, _lib.stream_ptr()))
-    return out
+    return _plan_stage(_lib.lib().dbx_patch_warp_plan, io, labels_i32, count, cfg, params, state, out)
 
 
 def apply_warp(patches, params, inv, count, out=None):
     """The dbx_patch_warp launch alone: patches uint8 [n, 240, 240, c] (any byte alignment) through the records params int32 [n, 16] and
     the matrices inv float64 [n, 9] into `out` (a new zeroed tensor when None; it may not overlap patches).  Slots at or past the count
     keep what they held."""
-    if patches.dtype != torch.uint8 or patches.dim() != 4 or tuple(patches.shape[1:3]) != (PATCH_SIDE, PATCH_SIDE) or not patches.is_contiguous():
-        raise RuntimeError('apply_warp: patches must be a contiguous uint8 [n, 240, 240, c] tensor, got %s %s' % (patches.dtype, list(patches.shape)))
-    if out is None:
-        out = torch.zeros_like(patches)
-    if out.dtype != torch.uint8 or out.shape != patches.shape or not out.is_contiguous():
-        raise RuntimeError('apply_warp: out must be a contiguous uint8 %s tensor, got %s %s' % (list(patches.shape), out.dtype, list(out.shape)))
+    out = _checked_out('apply_warp', patches, out)
     n = int(patches.size(0))
     if params.dtype != torch.int32 or params.numel() != 16 * n or inv.dtype != torch.float64 or inv.numel() != 9 * n \
             or not params.is_contiguous() or not inv.is_contiguous():
@@ -444,25 +454,44 @@ def warp_patches(patches, plan_or_labels, warp=None, params=None, counter=0):
     params: int [n, 16] records (injected mode), else they are drawn from (warp.seed, counter).  Returns (out, labels_i32, bbox, vertices,
     labels, params, fwd, inv): the warped patches, the four label tensors, the records used and the two matrices of every slot."""
     warp = warp if warp is not None else Warp()
-    dev = patches if torch.is_tensor(patches) else torch.from_numpy(np.ascontiguousarray(patches))
-    dev = dev.cuda()
-    n = int(dev.size(0))
-    parts = [warp.bank().reshape(-1), np.array([warp.seed, counter], dtype=np.int64)]
-    if params is not None:
-        rec = params.cpu().numpy() if torch.is_tensor(params) else np.asarray(params)
-        parts.append(np.ascontiguousarray(rec.astype(np.int32).reshape(n, 16)))
-    if isinstance(plan_or_labels, PatchPlan):
-        labels_in, count = plan_or_labels.labels_i32, plan_or_labels.count
-    else:
-        rows = plan_or_labels.cpu().numpy() if torch.is_tensor(plan_or_labels) else np.asarray(plan_or_labels)
-        parts += [np.ascontiguousarray(rows.astype(np.int32).reshape(n, 12)), np.array([n], dtype=np.int32)]
-        labels_in = count = None
-    up = _upload(*parts)
-    if labels_in is None:
-        labels_in, count = up[-2], up[-1]
-    plan = plan_warp(labels_in, count, warp.cfg(), bank=up[0].view(-1, 2), params=up[2] if params is not None else None, state=up[1])
-    out = apply_warp(dev, plan.params, plan.inv, count)
-    return out, plan.labels_i32, plan.bbox, plan.vertices, plan.labels, plan.params, plan.fwd, plan.inv
+    return _stage_patches(patches, plan_or_labels, warp, warp.bank().reshape(-1), params, counter,
+                          lambda rows, count, bank, rec, state: plan_warp(rows, count, warp.cfg(), bank=bank.view(-1, 2), params=rec, state=state),
+                          lambda dev, plan, count, bank: apply_warp(dev, plan.params, plan.inv, count), ('params', 'fwd', 'inv'))
+
+
+class _SamplerStage(object):
+    """A stage of a PatchSampler behind the cut: its uploaded bank, its own (seed, counter) state, its cfg struct, its plan and its pixel
+    buffer.  NAMES: the sampler's attribute for each of them and for the plan's records.  launch(labels_i32, pixels, count) makes the stage's two launches on the
+    stage before it and returns its own (labels_i32, pixels) for the next."""
+
+    def __init__(self, config, bank, plan, like):
+        flat, self.state = _upload(bank.reshape(-1) if len(bank) else np.zeros(256, np.uint8), np.array([config.seed, 0], dtype=np.int64))
+        self.bank = flat.view(-1, bank.shape[1])[:len(bank)]
+        self.cfg, self.plan, self.params, self.pixels = config.cfg(), plan, plan.params, torch.zeros_like(like)
+
+
+class _WarpStage(_SamplerStage):
+    NAMES = dict(bank='rot_bank', state='warp_state', cfg='warp_cfg', plan='warp_plan', params='warp_params', pixels='warped')
+
+    def __init__(self, warp, n, like):
+        _SamplerStage.__init__(self, warp, warp.bank(), WarpPlan(n, like.device), like)
+
+    def launch(self, labels_i32, pixels, count):
+        plan_warp(labels_i32, count, self.cfg, bank=self.bank, state=self.state, out=self.plan)
+        apply_warp(pixels, self.plan.params, self.plan.inv, count, self.pixels)
+        return self.plan.labels_i32, self.pixels
+
+
+class _AugStage(_SamplerStage):
+    NAMES = dict(bank='curves', state='aug_state', cfg='aug_cfg', plan='aug', params='aug_params', pixels='aug_patches')
+
+    def __init__(self, augment, n, like):
+        _SamplerStage.__init__(self, augment, augment.curves(), AugPlan(n, like.device), like)
+
+    def launch(self, labels_i32, pixels, count):
+        plan_augment(labels_i32, count, self.cfg, state=self.state, out=self.plan)
+        apply_augment(pixels, self.plan.params, count, self.bank, self.pixels)
+        return self.plan.labels_i32, self.pixels
 
 
 class PatchSampler(object):
@@ -492,37 +521,17 @@ class PatchSampler(object):
         self.plan = PatchPlan(self.M, self.n, self.table.device)
         self.patches = torch.zeros((self.n, PATCH_SIDE, PATCH_SIDE, self.c), dtype=torch.uint8, device=self.table.device)
         self.totals = torch.zeros(8, dtype=torch.int64, device=self.table.device)
-        self.warp = warp
-        if warp is not None:
-            self.rot_bank, self.warp_state = _upload(warp.bank().reshape(-1), np.array([warp.seed, 0], dtype=np.int64))
-            self.rot_bank = self.rot_bank.view(-1, 2)
-            self.warp_cfg = warp.cfg()
-            self.warp_plan = WarpPlan(self.n, self.table.device)
-            self.warped = torch.zeros_like(self.patches)
-        else:
-            self.warp_plan = self.warped = None
-        self.augment = augment
-        if augment is not None:
-            bank = augment.curves()
-            self.curves, self.aug_state = _upload(bank.reshape(-1) if len(bank) else np.zeros(256, np.uint8),
-                                                  np.array([augment.seed, 0], dtype=np.int64))
-            self.curves = self.curves.view(-1, 256)[:len(bank)]
-            self.aug_cfg = augment.cfg()
-            self.aug = AugPlan(self.n, self.table.device)
-            self.aug_patches = torch.zeros_like(self.patches)
+        self.warp, self.augment = warp, augment
+        self.warp_plan = self.warped = self.warp_params = self.aug_params = None
+        self.stages = [cls(config, self.n, self.patches) for cls, config in ((_WarpStage, warp), (_AugStage, augment)) if config is not None]
+        for stage in self.stages:                       # in launch order; the stage's tensors under the sampler's names for them
+            for k, name in stage.NAMES.items():
+                setattr(self, name, getattr(stage, k))
 
     @property
     def raw(self):
         """The un-augmented patches of the last batch (the sampler's own buffer)."""
         return self.patches
-
-    @property
-    def aug_params(self):
-        return self.aug.params if self.augment is not None else None
-
-    @property
-    def warp_params(self):
-        return self.warp_plan.params if self.warp is not None else None
 
     def launch(self):
         """The launches (and the tally's accumulation) on the current stream, without any read: what a graph capture holds."""
@@ -531,13 +540,8 @@ class PatchSampler(object):
         cut_patches(self.plan, self.c, self.patches)
         self.totals += self.plan.tally
         labels_i32, pixels = self.plan.labels_i32, self.patches
-        if self.warp is not None:
-            plan_warp(labels_i32, self.plan.count, self.warp_cfg, bank=self.rot_bank, state=self.warp_state, out=self.warp_plan)
-            apply_warp(pixels, self.warp_plan.params, self.warp_plan.inv, self.plan.count, self.warped)
-            labels_i32, pixels = self.warp_plan.labels_i32, self.warped
-        if self.augment is not None:
-            plan_augment(labels_i32, self.plan.count, self.aug_cfg, state=self.aug_state, out=self.aug)
-            apply_augment(pixels, self.aug.params, self.plan.count, self.curves, self.aug_patches)
+        for stage in self.stages:
+            labels_i32, pixels = stage.launch(labels_i32, pixels, self.plan.count)
 
     def next_batch(self, allow_short=None):
         """(patches uint8 [n, 240, 240, C], bbox [n, 4], vertices [n, 8], labels [n, 1], count): net.forward's and net.loss's inputs.
@@ -548,11 +552,8 @@ class PatchSampler(object):
         if count < self.n and not (self.allow_short if allow_short is None else allow_short):
             raise RuntimeError('PatchSampler: %d of %d candidates were accepted, fewer than n=%d; raise oversample (status tally: %s)'
                                % (count, self.M, self.n, self.plan.tally.tolist()))
-        if self.augment is not None:
-            return self.aug_patches, self.aug.bbox, self.aug.vertices, self.aug.labels, count
-        if self.warp is not None:
-            return self.warped, self.warp_plan.bbox, self.warp_plan.vertices, self.warp_plan.labels, count
-        return self.patches, self.plan.bbox, self.plan.vertices, self.plan.labels, count
+        plan, pixels = (self.stages[-1].plan, self.stages[-1].pixels) if self.stages else (self.plan, self.patches)
+        return pixels, plan.bbox, plan.vertices, plan.labels, count
 
     def status_tally(self):
         """{status name: candidates so far}, summed over every batch."""

@@ -2,7 +2,8 @@
 ends of its range, each blur kind (band seams and the four edges), all ops together, c = 1, 3, 4, input and output at odd byte
 addresses; dbx_patch_aug_plan's records and labels == the restatement's in injected and in device mode; slots past the count are left
 alone; the identity copies; overlap is refused; a PatchSampler with an Augment replays in a captured graph, and its batch is the
-restatement of its own raw patches and gives net.loss the restatement's labels."""
+restatement of its own raw patches and gives net.loss the restatement's labels; the band store at every destination offset 0..15, c = 1..4."""
+import functools
 import gc
 import os
 import sys
@@ -13,15 +14,13 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import aug_ref as A                                     # noqa: E402
+from patch_stage_util import GAMMAS, SENTINEL, _at_offset, _augment, _scene, _snap, _untouched      # noqa: E402
 
 import densebox_amd as D                                # noqa: E402
 from densebox_amd import data, synth                    # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
-GAMMAS = (0.6, 0.8, 1.25, 1.6)
-SIZES = [(97, 131), (300, 300), (260, 900), (1080, 1920)]            # (H, W)
 GROUPS = [A.CASES[k:k + 7] for k in range(0, len(A.CASES), 7)]       # 21 cases: three launches of n = 7
 
 
@@ -34,21 +33,6 @@ def bank():
 def _cfg_dict(augment):
     f = augment.cfg()
     return {k: (tuple(f.kind_w) if k == 'kind_w' else getattr(f, k)) for k in A.CFG_DEFAULT}
-
-
-def _at_offset(n, c, offset, fill=None):
-    """(arena, view): a uint8 [n, 240, 240, c] view that starts `offset` bytes into an arena of sentinel bytes."""
-    size = n * 240 * 240 * c
-    arena = torch.full((size + 64,), SENTINEL, dtype=torch.uint8, device='cuda')
-    view = arena[offset:offset + size].view(n, 240, 240, c)
-    if fill is not None:
-        view.copy_(torch.from_numpy(fill))
-    assert view.data_ptr() % 16 == offset % 16
-    return arena, view
-
-
-def _untouched(arena, offset, size):
-    return bool((arena[:offset] == SENTINEL).all()) and bool((arena[offset + size:] == SENTINEL).all())
 
 
 def _launch(host_patches, recs, rows, dbank, count=None, in_off=33, out_off=17):
@@ -219,31 +203,36 @@ def test_overlapping_input_and_output_is_refused(bank):
     assert not arena.any()
 
 
-def _plate(rs, W, H):
-    w, h = int(rs.randint(4, min(200, W // 3) + 1)), int(rs.randint(4, min(80, H // 3) + 1))
-    x, y = int(rs.randint(0, W - w)), int(rs.randint(0, H - h))
-    pts = [(x, y), (x + w, y), (x + w, y + h), (x, y + h)]
-    return [v for k in rs.permutation(4) for v in pts[k]]
+BAND_RECORDS = {'flip + binomial 3 x 3': A.record(blur=1, flags=1), 'identity (the copy path)': A.record()}
 
 
-def _scene(seed=3):
-    rs = np.random.RandomState(seed)
-    frames = [rs.randint(0, 256, size=(h, w, 3)).astype(np.uint8) for h, w in SIZES]
-    plates = [[_plate(rs, w, h) for _ in range(k)] for (h, w), k in zip(SIZES, (5, 4, 6, 12))]
-    return frames, plates
+@functools.lru_cache(maxsize=None)
+def _band_case(c, kind):
+    """(patch, restatement) of one slot through BAND_RECORDS[kind]: made once per c and kind, shared by the 16 offsets."""
+    patch = np.random.RandomState(40 + c).randint(0, 256, size=(1, 240, 240, c)).astype(np.uint8)
+    want = A.augment(patch[0], BAND_RECORDS[kind], A.gamma_bank(GAMMAS))
+    want.setflags(write=False)
+    return patch, want
 
 
-def _augment():
-    return data.Augment(flip=0.5, blur=0.6, curve=0.5, noise_p=0.6, gammas=GAMMAS, seed=23)
+@pytest.mark.parametrize('kind', sorted(BAND_RECORDS))
+@pytest.mark.parametrize('out_off', range(16))
+@pytest.mark.parametrize('c', [1, 2, 3, 4])
+def test_the_band_store_at_every_destination_offset(bank, c, out_off, kind):
+    """n = 1 (15 workgroups): patch_band_store's 16-byte words, dwords and bytes at every offset of the destination inside a 16-byte
+    word, source at offset 33; the output is the restatement bit for bit and no byte outside the view is written."""
+    patch, want = _band_case(c, kind)
+    out, arena, _ = _launch(patch, [BAND_RECORDS[kind]], np.zeros((1, 12), np.int32), bank[1], in_off=33, out_off=out_off)
+    assert out.data_ptr() % 16 == out_off
+    bad = np.argwhere(out[0].cpu().numpy() != want)
+    assert len(bad) == 0, (kind, c, out_off, len(bad), bad[:4].tolist())
+    assert _untouched(arena, out_off, patch.size)
+    assert (kind == 'identity (the copy path)') == np.array_equal(want, patch[0])
 
 
 def _sampler(seed, n=7, **kw):
     frames, plates = _scene()
     return data.PatchSampler(frames, plates, n, oversample=4.0, neg_frac=0.2, seed=seed, augment=_augment(), **kw)
-
-
-def _snap(s):
-    return [t.clone() for t in (s.aug_patches, s.aug.labels_i32, s.aug.bbox, s.aug.vertices, s.aug.labels, s.aug.params, s.patches)]
 
 
 def test_three_eager_calls_equal_three_replays_of_one_captured_graph():
