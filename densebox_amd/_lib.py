@@ -97,6 +97,28 @@ class ShotRecord(C.Structure):
     _fields_ = [('stream', C.c_int32), ('slot', C.c_int32), ('shot', Shot)]
 
 
+class ZoneLine(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ('ax', 'ay', 'bx', 'by')]
+
+
+class ZonePoly(C.Structure):
+    _fields_ = [('n', C.c_int32), ('role', C.c_int32), ('xy', C.c_int32 * 32)]
+
+
+class ZoneConfig(C.Structure):
+    _fields_ = [('n_lines', C.c_int32), ('n_regions', C.c_int32), ('n_masks', C.c_int32), ('reserved', C.c_int32),
+                ('lines', ZoneLine * 8), ('regions', ZonePoly * 8), ('masks', ZonePoly * 8)]
+
+
+class ZoneState(C.Structure):
+    _fields_ = [('owner_id', C.c_int32), ('has_prev', C.c_int32), ('px', C.c_int32), ('py', C.c_int32), ('inside', C.c_int32),
+                ('reserved', C.c_int32 * 3)]
+
+
+class ZoneEvent(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ('stream', 'track_id', 'kind', 'index', 'frame', 'hits', 'ax', 'ay')]
+
+
 class OverlayFrame(C.Structure):
     _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('h', C.c_int32), ('w', C.c_int32)]
 
@@ -253,6 +275,11 @@ SIGNATURES = {
     'dbx_redact_batch': (C.c_int, [_VP, _I32, _I32, _I32, _I32, _VP, _I32, _I64, _VP, _VP, _I32, _VP, _I32, _I32, _I32,
                                    C.POINTER(RedactStyle), _VP]),
     'dbx_redact_host': (C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP, _I32, _I32, _VP, _I32, _VP, _I32, C.POINTER(RedactStyle)]),
+    'dbx_zone_filter_keep': (C.c_int, [_VP, _I32, _I64, _VP, _VP, _I32, _I32, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
+    'dbx_zone_update_batch': (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
+    'dbx_zone_append': (C.c_int, [_VP, _VP, _I32, _I32, _VP, _I64, _VP, _VP]),
+    'dbx_zone_check_config': (C.c_int, [C.POINTER(ZoneConfig)]),
+    'dbx_zone_host': (C.c_int, [_I32, _I64, _VP, _VP, _VP]),
     'dbx_resize_batch_workspace_bytes': (_I64, [_I32]),
     'dbx_resize_cubic_batch_u8': (C.c_int, [C.POINTER(ResizeJob), _I32, _I32, _VP, _VP, _VP]),
     'dbx_nv12_to_rgb_batch': (C.c_int, [_VP, _I32, _I32, _I32, C.POINTER(Nv12Params), _VP]),

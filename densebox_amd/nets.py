@@ -165,6 +165,15 @@ class _DenseBoxBase(nn.Module):
         return track_batch(self, images, tracker=tracker, stream0=stream0, K=K, score_thresh=score_thresh, max_dets=max_dets,
                            nms_thresh=nms_thresh, max_batch=max_batch)
 
+    def watch_batch(self, images, *, tracker, zones, stream0=0, K=10, score_thresh=None, max_dets=1024, nms_thresh=0.4, max_batch=32):
+        """track_batch() with zones (a zones.Zones made for `tracker`): the keep lists filtered by the streams' include / exclude
+        polygons in front of the tracking update, line crossings and region events counted behind it, all on the device and, in eval
+        mode, in one hipGraph per chunk: a list of (dets, filtered keep, track_id, track_hits) in input order
+        (densebox_amd.zones.watch_batch)."""
+        from .zones import watch_batch
+        return watch_batch(self, images, tracker=tracker, zones=zones, stream0=stream0, K=K, score_thresh=score_thresh,
+                           max_dets=max_dets, nms_thresh=nms_thresh, max_batch=max_batch)
+
     def track_plate_crops(self, images, *, tracker, gallery, stream0=0, K=10, nms_thresh=0.4, max_batch=32):
         """track_batch() on uint8 frames with the best plate crop of every track kept on the device in `gallery` (a
         gallery.PlateGallery made for `tracker`), in eval mode in one hipGraph per chunk: a list of (dets, keep, track_id, track_hits) in

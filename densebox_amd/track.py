@@ -125,11 +125,13 @@ class Tracker:
 
 
 # ------------------------------------------------------------------------------------------------------------ the launches
-def _launch(tr, rows, stream0, dry=False, gallery=None):
+def _launch(tr, rows, stream0, dry=False, gallery=None, between=None):
     """dbx_track_update_batch + dbx_track_append on the device rows `rows` (rows.Rows), for streams stream0 .. stream0 + B - 1 of tracker
     `tr`.  gallery = (gal, crops, ok): dbx_track_gallery_update runs between the two, crops uint8 [B, slots, oh, ow, c] and ok int32
     [B, slots] being what dbx_plate_crops_batch wrote with sel = keep.  dry: the launches advance a scratch copy of the state and
-    append nothing, and the gallery's reads it and writes nothing (commit = 0).  Returns device tensors (ids int32 [2, B, slots] =
+    append nothing, and the gallery's reads it and writes nothing (commit = 0).  between(base, o_tab): called behind the update (and
+    the gallery's launch) and before the append with the address of the state the update advanced and the table's offset in it, for
+    launches that read the table there (zones._launch).  Returns device tensors (ids int32 [2, B, slots] =
     (track_id, track_hits), track_slot int32 [B, slots], retired uint8, tally int32 [B, 6])."""
     dev, B, slots = rows.dets.device, rows.B, rows.slots
     state, records = tr._buffers(dev)
@@ -156,6 +158,8 @@ def _launch(tr, rows, stream0, dry=False, gallery=None):
                                          C.c_void_p(arena.data_ptr() + gal.capacity * SHOT_RECORD.itemsize), ptr(gstate), B, slots,
                                          tr.streams, stream0, tr.max_tracks, gal.oh, gal.ow, gal.channels, gal.capacity,
                                          POLICIES[gal.policy], gal.min_score, 0 if dry else 1, stream_ptr()))
+    if between is not None:
+        between(base, o_tab)
     check(L.dbx_track_append(ptr(retired), ptr(tally), B, tr.max_tracks, stream0, None if dry else ptr(records), 0 if dry else tr.capacity,
                              C.c_void_p(base + o_app), stream_ptr()))
     return ids, slot, retired, tally

@@ -79,7 +79,10 @@ const char* dbx_last_error(void);
  *      additions likewise
  *      also at 13, without a bump: dbx_nv12_frame, dbx_nv12_params, dbx_resize_job_nv12, dbx_nv12_to_rgb_batch, dbx_rgb_to_nv12_batch,
  *      dbx_nv12_host, dbx_resize_batch_nv12_workspace_bytes, dbx_resize_cubic_batch_nv12 (NV12 frames converted to and from RGB and
- *      resized straight from the surface), pure additions likewise */
+ *      resized straight from the surface), pure additions likewise
+ *      also at 13, without a bump: dbx_zone_line, dbx_zone_poly, dbx_zone_config, dbx_zone_state, dbx_zone_event, dbx_zone_filter_keep,
+ *      dbx_zone_update_batch, dbx_zone_append, dbx_zone_check_config, dbx_zone_host (region-of-interest filter, line crossings and
+ *      region events behind the tracker), pure additions likewise */
 #define DBX_ABI_VERSION 13
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
@@ -993,6 +996,118 @@ int dbx_redact_batch(const dbx_overlay_frame* frames, int32_t batch, int32_t c, 
                      void* stream);
 int dbx_redact_host(const uint8_t* src, uint8_t* dst, int32_t h, int32_t w, int32_t c, const double* rows, int32_t det_cols, int32_t n,
                     const int32_t* keep, int32_t k, const dbx_track* tracks, int32_t ntracks, const dbx_redact_style* style);
+
+/* ---- zones behind the tracker (no reference counterpart): a region-of-interest filter on the keep lists, counted line crossings and
+ * region enter / exit events of the tracks, all on the device.  The semantics are this project's own, restated in plain integers by
+ * tests/zones_ref.py ----
+ * Coordinates: all geometry is in QUARTER PIXELS, int32 with |v| <= 2^20; every product is taken in int64 (a cross product of two
+ * differences is at most 2^43 in magnitude for configured points, 2^47 with anchors).  A front end converts a user's float v with
+ * int(floor(4 * v + 0.5)) and refuses non-finite values and values out of range.
+ * Anchor of a box (x1, y1, x2, y2), float64: valid when all four values are finite with |v| < 2^20 (dbx_redact_batch's landmark rule).
+ * ax = floor((x1 + x2) * 2.0 + 0.5); ay = floor((y1 + y2) * 2.0 + 0.5) for anchor = 0 (centre), ay = floor(y2 * 4.0 + 0.5) for anchor = 1
+ * (bottom); evaluated in exactly this order, one IEEE operation per written operation, no contraction.
+ * Configuration: dbx_zone_config [streams], a device table written from the host and never changed by a launch: per stream up to 8
+ * directed lines A -> B (A != B), 8 count regions and 8 mask polygons, each mask marked include (role 0) or exclude (role 1); a region's
+ * role is 0.  A polygon has 3..16 vertices in either orientation, may be concave and may intersect itself.
+ * Point in polygon: even-odd.  Edge (xi, yi) -> (xj, yj), j = i + 1 mod n, counts when (yi > py) != (yj > py) and, with d = yj - yi,
+ * l = (px - xi) * d, r = (xj - xi) * (py - yi): l < r if d > 0, else l > r.  Inside when the count is odd.  (Half-open: of an axis-aligned
+ * rectangle the edges at the smaller x and the smaller y belong to it, the other two do not; a horizontal edge never counts.)
+ * Side of a line: side(P) = cross(B - A, P - A) >= 0, cross(u, v) = ux * vy - uy * vx.
+ * Crossing: the move P0 -> P1 crosses A -> B when side(P0) != side(P1) and, with t(Q) = cross(P1 - P0, Q - P0),
+ * (t(A) >= 0) != (t(B) >= 0).  Forward (kind 0) when side goes false -> true, backward (kind 1) otherwise.  (A point ON the line has
+ * side true, so landing on the line from the false side is the crossing and leaving it to the true side is none.)
+ *
+ * dbx_zone_filter_keep: ONE launch, a workgroup of 256 threads per frame; capturable.  It reads the rows and keep lists of the decoded-rows
+ * description (both layouts, through the same reading rule as dbx_track_update_batch; frame b belongs to stream stream0 + b) and writes
+ * keep_out, a buffer of the same layout and size (keep_out != keep).  With k the clamped count and E = min(rows of the frame, slots):
+ * a stream without mask polygons has its k entries copied as they are; otherwise an entry stays when it names a row of the frame, the
+ * row's anchor is valid, the anchor is inside at least one include polygon (or the stream has none) and inside no exclude polygon.  The
+ * survivors keep their order; word 0 is the new count and the words behind the survivors up to position E are 0.  A frame of the packed
+ * layout with a corrupt prefix pair has no list and nothing of keep_out is written for it (pairs that are each valid but overlap one
+ * another give lists that overlap in keep_out as they do in keep: in bounds, their content unspecified).  stats: int32 [batch][2] = (k, survivors).
+ * LDS: the stream's mask polygons, 1088 bytes, and 16 bytes of wave totals.
+ *
+ * dbx_zone_update_batch: ONE launch, a workgroup per frame, a thread per track slot; capturable.  It runs BEHIND dbx_track_update_batch
+ * of the same frames, on the tracker's table and headers; frame f = headers[s].frame - 1.  Zone state: dbx_zone_state
+ * [streams][max_tracks], 32 bytes: owner_id (-1 initially, the rest 0), has_prev, px, py, inside (bit r: region r), reserved.  For the
+ * slots t of stream s in ascending order, K = tracks[s][t], Z = state[s][t], events in this order:
+ *   1  owner left   Z.owner_id >= 0 and K.id != Z.owner_id (the slot is free or holds another id): for every bit r set in Z.inside,
+ *                   ascending over all 8, an event of kind 4 ("ended inside") with the old owner's id, hits 0 and the stored (px, py);
+ *                   exits[r] += 1, occupancy[r] -= 1.  Then Z = (-1, 0, 0, 0, 0).
+ *   2  crossings    K.id >= 0 and K.hits >= min_hits (else the slot is done).  When K.id != Z.owner_id: owner_id = K.id, has_prev = 0,
+ *                   inside = 0.  With a valid anchor P of K.box and has_prev: for every line l < n_lines, ascending, when (px, py) -> P
+ *                   crosses it an event of kind 0 or 1 and forward[l] += 1 or backward[l] += 1.
+ *   3  transitions  with a valid anchor: for every region r < n_regions, ascending, when "P is inside region r" differs from bit r of
+ *                   inside an event of kind 2 (enter: enters[r] += 1, occupancy[r] += 1) or 3 (exit: exits[r] += 1, occupancy[r] -= 1)
+ *                   and the bit flips; bits of regions not configured stay.  Then (px, py) = P, has_prev = 1.  With an invalid anchor:
+ *                   no events, has_prev = 0, inside as it is.
+ * A live slot with hits < min_hits leaves no zone state, so a track first seen inside a region enters it in the first frame it
+ * qualifies.  A coasting track counts like any other: its box is the prediction.  An event is a dbx_zone_event, 32 bytes: stream,
+ * track_id, kind, index (line or region), frame, hits (K.hits; 0 for kind 4), ax, ay (P; the stored point for kind 4).  The events of
+ * frame b go to staged[b][0 .. staged_count[b] - 1], staged being dbx_zone_event [batch][max_tracks * 24] (per slot at most 8 ended
+ * inside + 8 crossings + 8 transitions); staged and dbx_zone_append's events are 16-byte aligned.  line_counts: int64 [streams][8][2] = (forward, backward); region_counts:
+ * int64 [streams][8][3] = (enters, exits, occupancy).  commit = 0 reads everything and writes NOTHING (state, counters, staged and
+ * staged_count included): the dry mode of a graph's warm-up runs, as in dbx_track_gallery_update.  LDS: the stream's table, 2320 bytes,
+ * 160 bytes of counter deltas and 16 bytes of wave totals; no scratch buffer beyond staged.
+ *
+ * dbx_zone_append: one small launch behind the update, dbx_track_append's pattern: the staged events of the call go to events[cursor...]
+ * in frame order, then staging order; staged_count[b] is clamped to 0..max_tracks * 24.  state: device int64 [4] = {cursor, dropped,
+ * total, reserved}; events past `capacity` are counted in dropped and not written.
+ *
+ * Robustness: nothing outside the buffers is read or written, whatever device data says: counts read from device memory (keep counts,
+ * n_lines, n_regions, n_masks, a polygon's n, staged_count) are clamped before they bound a loop, table coordinates are clamped to
+ * +-2^20 on the way to LDS, ids, hits and boxes are data.  A corrupt prefix pair gives an empty frame: its tracks coast and the zone
+ * update still runs.  Refused with DBX_ERR_ARG before anything is queued: batch < 0, stream0 < 0 or stream0 + batch > streams, slots
+ * outside 1..1024, det_cols not 5 or 13, det_rows < 0 (or below batch * slots in slot layout), max_tracks outside 1..256, min_hits < 1,
+ * an anchor other than 0 / 1, capacity < 0, a null pointer (events only when capacity is 0), keep_out == keep.  batch == 0: no-op.
+ *
+ * dbx_zone_check_config validates a HOST copy of one stream's table: the three counts in 0..8 and, for the entries below them, a
+ * polygon's n in 3..16, every coordinate within +-2^20, A != B, a region's role 0 and a mask's role 0 or 1.
+ * dbx_zone_host runs the kernels' own geometry functions on the CPU (no GPU needed), n cases per call: op 0 / 1 the centre / bottom
+ * anchor of boxes float64 [n][4] -> out int32 [n][3] = (valid, ax, ay); op 2 side of ints [n][6] = (ax, ay, bx, by, px, py) -> out [n]
+ * = 0 / 1; op 3 crossing of ints [n][8] = (ax, ay, bx, by, x0, y0, x1, y1) -> out [n] = -1 none, 0 forward, 1 backward; op 4 point in
+ * polygon of ints [n][35] = (px, py, n, xy[32]) -> out [n] = 0 / 1.
+ *
+ * Layouts: dbx_zone_line 16 bytes (ax 0, ay 4, bx 8, by 12); dbx_zone_poly 136 bytes (n 0, role 4, xy 8: x, y interleaved);
+ * dbx_zone_config 2320 bytes (n_lines 0, n_regions 4, n_masks 8, reserved 12, lines 16, regions 144, masks 1232); dbx_zone_state 32
+ * bytes (owner_id 0, has_prev 4, px 8, py 12, inside 16, reserved 20); dbx_zone_event 32 bytes (stream 0, track_id 4, kind 8, index 12,
+ * frame 16, hits 20, ax 24, ay 28). */
+typedef struct dbx_zone_line { int32_t ax, ay, bx, by; } dbx_zone_line;
+typedef struct dbx_zone_poly {
+    int32_t n;             /* 3..16 vertices */
+    int32_t role;          /* masks: 0 include, 1 exclude; regions: 0 */
+    int32_t xy[32];        /* x0, y0, x1, y1, ... in quarter pixels */
+} dbx_zone_poly;
+typedef struct dbx_zone_config {
+    int32_t n_lines, n_regions, n_masks, reserved;
+    dbx_zone_line lines[8];
+    dbx_zone_poly regions[8];
+    dbx_zone_poly masks[8];
+} dbx_zone_config;
+typedef struct dbx_zone_state {
+    int32_t owner_id;      /* the track id the slot's zone state belongs to; -1 none */
+    int32_t has_prev;      /* (px, py) is the anchor of the previous frame */
+    int32_t px, py;
+    int32_t inside;        /* bit r: inside region r */
+    int32_t reserved[3];
+} dbx_zone_state;
+typedef struct dbx_zone_event {
+    int32_t stream, track_id;
+    int32_t kind;          /* 0 forward crossing, 1 backward crossing, 2 enter, 3 exit, 4 ended inside */
+    int32_t index;         /* the line (kinds 0, 1) or the region */
+    int32_t frame, hits, ax, ay;
+} dbx_zone_event;
+int dbx_zone_filter_keep(const double* dets, int32_t det_cols, int64_t det_rows, const int32_t* keep, const int32_t* prefix, int32_t batch,
+                         int32_t slots, const dbx_zone_config* config, int32_t streams, int32_t stream0, int32_t anchor,
+                         int32_t* keep_out, int32_t* stats, void* stream);
+int dbx_zone_update_batch(const dbx_track* tracks, const int32_t* headers, const dbx_zone_config* config, dbx_zone_state* state,
+                          int64_t* line_counts, int64_t* region_counts, int32_t batch, int32_t streams, int32_t stream0,
+                          int32_t max_tracks, int32_t min_hits, int32_t anchor, dbx_zone_event* staged, int32_t* staged_count,
+                          int32_t commit, void* stream);
+int dbx_zone_append(const dbx_zone_event* staged, const int32_t* staged_count, int32_t batch, int32_t max_tracks, dbx_zone_event* events,
+                    int64_t capacity, int64_t* state, void* stream);
+int dbx_zone_check_config(const dbx_zone_config* config);
+int dbx_zone_host(int32_t op, int64_t n, const double* boxes, const int32_t* ints, int32_t* out);
 
 /* ---- batched pad + bicubic resize (pad_img + cv2.resize(..., INTER_CUBIC), DenseBox.py:1282-1340; the patch cutters' resize of a
  * cropped window) ----
