@@ -212,6 +212,14 @@ class MergeXform(C.Structure):
     _fields_ = [('scale', C.c_double), ('off_x', C.c_double), ('off_y', C.c_double)]
 
 
+class Tile(C.Structure):
+    _fields_ = [('frame', C.c_int32), ('x0', C.c_int32), ('y0', C.c_int32), ('side', C.c_int32), ('cw', C.c_int32), ('ch', C.c_int32),
+                ('scale', C.c_double), ('lo2x', C.c_double), ('hi2x', C.c_double), ('lo2y', C.c_double), ('hi2y', C.c_double)]
+
+
+TILE_RULE_NONE, TILE_RULE_CORE = 0, 1
+
+
 _VP, _I32, _I64, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 _PV, _PC = C.POINTER(View), C.POINTER(ConvDesc)
 
@@ -355,6 +363,12 @@ SIGNATURES = {
     'dbx_merge_nms_thresh_batch_workspace_bytes': (_I64, [_I32, _I32, _I32]),
     'dbx_merge_nms_thresh_batch': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(MergeXform), _I32, _I32, _I32, _I32, _D,
                                              _VP, _VP, _VP, _VP, _VP]),
+    'dbx_tile_grid': (C.c_int, [_I32, _I32, _I32, _I32, _VP, _I32]),
+    'dbx_tile_stage_bytes': (_I64, [_I32, _I32, _I32]),
+    'dbx_tile_rows_batch': (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
+    'dbx_tile_nms_batch_workspace_bytes': (_I64, [_I32, _I32, _I32]),
+    'dbx_tile_nms_batch': (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _D, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    'dbx_tile_host': (C.c_int, [_I32, _I64, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP]),
 }
 
 ABI_VERSION = 13         # include/densebox_hip.h DBX_ABI_VERSION this binding was written against

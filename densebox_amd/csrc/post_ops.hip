@@ -3,6 +3,7 @@
 // file: `areas[i] + areas[j] - w*h` must round the product before the subtraction like NumPy does.
 #pragma clang fp contract(off)
 #include "common.hpp"
+#include "nms_large.hpp"
 #include "warp_px.hpp"
 
 #include <cmath>
@@ -69,7 +70,7 @@ extern "C" int dbx_grad_guard(const float* grads, int64_t n, int32_t* guard, int
 }
 
 // ---------------------------------------------------------------------------------------------- top-K + decode
-#define DET_THREADS 1024
+// (DET_THREADS, the workgroup width of the decode and the small NMS, is nms_large.hpp's)
 
 __device__ __forceinline__ void block_argmax_g(const float* vals, int n, float* red_v, int* red_i, float& ov, int& oi) {
     const int tid = threadIdx.x;
@@ -695,10 +696,8 @@ extern "C" int dbx_merge_nms_batch(const double* const* level_dets, const dbx_me
 //      the diagonal, with nms_block's fp64 expression; workgroups past n_b leave at once.  Many CUs per image.
 //   3. thresh_sweep_kernel, one wave per image: the greedy walk with the removed set in registers (lane w holds word w of 64).
 // dbx_nms_large runs 2 (without the copy) and 3 on caller rows behind a sort of (score key, row index) pairs.
-#define THR_MAX_DETS 4096
-#define NMSL_THREADS 256
-
-static __host__ __device__ inline long long thr_up256(long long v) { return (v + 255) / 256 * 256; }
+// nmsl_mask_rows, nmsl_sweep, nmsl_score_key and nmsl_sort_pairs live in nms_large.hpp: the tile stitch (tile_ops.hip) runs the same
+// functions.
 // one image's scratch slice: rows [cap][13] float64 | map indices [cap] int64 | NMS order [cap] int32 | matrix [cap][ceil(cap / 64)] words
 struct ThrLayout { long long topk, order, mask, total; int nw; };
 static __host__ __device__ inline ThrLayout thr_layout(int cap) {
@@ -808,81 +807,6 @@ __global__ __launch_bounds__(DET_THREADS) void thresh_rows_kernel(const ThrArgs 
     thresh_select_image<false>(a, a.dets + r0 * a.dc, a.topk + r0, nullptr);
 }
 
-// Rows [64 rb, 64 rb + 64) (in NMS order: position p is row order[p] of dets) of the n x nw suppression matrix, the words at or right of
-// the diagonal: bit q of row p (q > p) = box p suppresses box q, nms_block's expression.  Words left of the diagonal are never written
-// and never read.  NMSL_THREADS threads: lane = row, the four waves share the words; a wave stages the 64 column boxes of its word
-// in LDS (10 KB in all) and every lane reads them back as broadcasts.
-__device__ __forceinline__ void nmsl_mask_rows(const double* dets, int dc, const int* order, int n, double thresh,
-                                               unsigned long long* mask, int nw_stride, int rb) {
-    __shared__ double cb[NMSL_THREADS / 64][5][64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int p = rb * 64 + lane, nw = (n + 63) >> 6;
-    double x1 = 0, y1 = 0, x2 = 0, y2 = 0, ai = 0;
-    if (p < n) {
-        const double* d = dets + (size_t)order[p] * dc;
-        x1 = d[0]; y1 = d[1]; x2 = d[2]; y2 = d[3];
-        ai = (x2 - x1 + 1) * (y2 - y1 + 1);
-    }
-    for (int w0 = rb; w0 < nw; w0 += NMSL_THREADS / 64) {            // (uniform trip count: the barriers are reached by every wave)
-        const int w = w0 + wv, q0 = 64 * w + lane;
-        if (q0 < n) {
-            const double* d = dets + (size_t)order[q0] * dc;
-            const double u1 = d[0], v1 = d[1], u2 = d[2], v2 = d[3];
-            cb[wv][0][lane] = u1; cb[wv][1][lane] = v1; cb[wv][2][lane] = u2; cb[wv][3][lane] = v2;
-            cb[wv][4][lane] = (u2 - u1 + 1) * (v2 - v1 + 1);
-        }
-        __syncthreads();
-        if (w < nw && p < n) {
-            unsigned long long bits = 0ull;
-            const int cn = min(64, n - 64 * w);
-            for (int c = 0; c < cn; ++c) {
-                if (64 * w + c <= p) continue;
-                const double xx1 = fmax(x1, cb[wv][0][c]), yy1 = fmax(y1, cb[wv][1][c]), xx2 = fmin(x2, cb[wv][2][c]), yy2 = fmin(y2, cb[wv][3][c]);
-                const double ww = fmax(0.0, xx2 - xx1 + 1), hh = fmax(0.0, yy2 - yy1 + 1);
-                const double inter = ww * hh;
-                const double ovr = inter / (ai + cb[wv][4][c] - inter);
-                if (!(ovr <= thresh)) bits |= 1ull << c;             // NaN is dropped, like np.where(ovr <= t)
-            }
-            mask[(size_t)p * nw_stride + w] = bits;
-        }
-        __syncthreads();
-    }
-}
-
-// The greedy walk by ONE wave: lane w holds word w of the removed set, the matrix rows come in blocks of 32 with the next block's loads
-// in flight while this one is walked.  keep[0] = count, keep[1..] = kept rows in NMS order.
-__device__ __forceinline__ void nmsl_sweep(const unsigned long long* mask, int nw_stride, const int* order, int n, int* keep) {
-    const int lane = threadIdx.x & 63, nw = (n + 63) >> 6;
-    unsigned long long removed = 0ull, cur[32], nxt[32];
-    int cnt = 0, ord_c = 0, ord_n = 0;
-#pragma unroll
-    for (int r = 0; r < 32; ++r) cur[r] = (lane < nw && r < n) ? mask[(size_t)r * nw_stride + lane] : 0ull;
-    if (lane < 32 && lane < n) ord_c = order[lane];
-    for (int p0 = 0; p0 < n; p0 += 32) {
-        const int p1 = p0 + 32;
-#pragma unroll
-        for (int r = 0; r < 32; ++r) nxt[r] = (lane < nw && lane >= (p1 >> 6) && p1 + r < n) ? mask[(size_t)(p1 + r) * nw_stride + lane] : 0ull;
-        ord_n = (lane < 32 && p1 + lane < n) ? order[p1 + lane] : 0;
-#pragma unroll
-        for (int r = 0; r < 32; ++r) {
-            const int pos = p0 + r;
-            if (pos < n) {
-                const unsigned long long word = __shfl(removed, pos >> 6);
-                if (!((word >> (pos & 63)) & 1ull)) {              // (uniform) box `pos` survives
-                    const int row = __shfl(ord_c, r);
-                    if (lane == 0) keep[1 + cnt] = row;
-                    ++cnt;
-                    removed |= cur[r];
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 32; ++r) cur[r] = nxt[r];
-        ord_c = ord_n;
-    }
-    if (lane == 0) keep[0] = cnt;
-}
-
 __global__ __launch_bounds__(NMSL_THREADS) void thresh_pack_mask_kernel(const ThrArgs a) {
     const int rb = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int n = a.counts[2 * b];
@@ -987,26 +911,6 @@ extern "C" int dbx_thresh_rows_batch(const float* score, const float* loc, const
 // ---- dbx_nms_large: the same matrix + sweep on caller rows.  The order comes from a bitonic sort of (score key, row) pairs in LDS
 // (48 KB): key = the float64 score's bits made order-preserving, -0 == +0, every NaN the largest; larger key first, the higher row first
 // among equal keys -- nms_block's rank for every input.
-__device__ __forceinline__ unsigned long long nmsl_score_key(double sc) {
-    if (sc != sc) return ~0ull;
-    if (sc == 0.0) return 0x8000000000000000ull;
-    const unsigned long long u = (unsigned long long)__double_as_longlong(sc);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-// bitonic sort of the (key, row) pairs [0, P2) in LDS by a DET_THREADS-wide workgroup into that order (a barrier in front is the caller's)
-__device__ __forceinline__ void nmsl_sort_pairs(unsigned long long* key, int* row, int P2) {
-    for (int size = 2; size <= P2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < (P2 >> 1); t += DET_THREADS) {
-                const int i = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), j = i | stride;
-                const unsigned long long x = key[i], y = key[j];
-                const int ri = row[i], rj = row[j];
-                const bool i_less = x < y || (x == y && ri < rj);
-                if (((i & size) == 0) == i_less) { key[i] = y; key[j] = x; row[i] = rj; row[j] = ri; }
-            }
-            __syncthreads();
-        }
-}
 __global__ __launch_bounds__(DET_THREADS) void nms_large_order_kernel(const double* dets, int n, int dc, int* order) {
     __shared__ unsigned long long key[THR_MAX_DETS];
     __shared__ int row[THR_MAX_DETS];

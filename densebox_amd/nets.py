@@ -234,6 +234,15 @@ class _DenseBoxBase(nn.Module):
         from .decode import detect_pyramid
         return detect_pyramid(self, images, sizes, K, nms_thresh, max_batch, score_thresh, max_dets, with_levels)
 
+    def detect_tiled(self, frames, tile=512, src=None, overlap=128, K=10, score_thresh=None, max_dets=64, nms_thresh=0.4, max_batch=32,
+                     rule='core', roi=None, with_tiles=False):
+        """Sliced inference for large frames: every frame cut into overlapping src x src windows resized to tile x tile, the tiles of
+        all frames forwarded in chunks of one fixed shape, and the rows stitched per frame on the device -- source-frame coordinates,
+        only the rows whose tile owns the box centre, ONE NMS per frame; a list of (dets[m_b, 5|13], keep) in input order
+        (densebox_amd.tiles.detect_tiled)."""
+        from .tiles import detect_tiled
+        return detect_tiled(self, frames, tile, src, overlap, K, score_thresh, max_dets, nms_thresh, max_batch, rule, roi, with_tiles)
+
 
 class DenseBox(_DenseBoxBase):
     KIND = 'DenseBox'

@@ -82,7 +82,10 @@ const char* dbx_last_error(void);
  *      resized straight from the surface), pure additions likewise
  *      also at 13, without a bump: dbx_zone_line, dbx_zone_poly, dbx_zone_config, dbx_zone_state, dbx_zone_event, dbx_zone_filter_keep,
  *      dbx_zone_update_batch, dbx_zone_append, dbx_zone_check_config, dbx_zone_host (region-of-interest filter, line crossings and
- *      region events behind the tracker), pure additions likewise */
+ *      region events behind the tracker), pure additions likewise
+ *      also at 13, without a bump: dbx_tile, dbx_tile_grid, dbx_tile_stage_bytes, dbx_tile_rows_batch,
+ *      dbx_tile_nms_batch_workspace_bytes, dbx_tile_nms_batch, dbx_tile_host (tiled detection: the plan of a large frame and the
+ *      per-frame stitch of the tiles' rows on the device), pure additions likewise */
 #define DBX_ABI_VERSION 13
 int dbx_version(void);
 /* device sanity: returns gfx arch number (950) of `device`, or <0 */
@@ -604,6 +607,82 @@ int64_t dbx_merge_nms_thresh_batch_workspace_bytes(int32_t levels, int32_t batch
 int dbx_merge_nms_thresh_batch(const double* const* level_dets, const int32_t* const* level_counts, const dbx_merge_xform* xform,
                                int32_t levels, int32_t batch, int32_t max_dets, int32_t det_cols, double nms_thresh,
                                double* out_dets, int32_t* out_keep, int32_t* out_counts, void* workspace, void* stream);
+
+/* ---- tiled detection: a large frame cut into overlapping fixed-size windows ("tiles", optionally magnified), all tiles of all frames
+ * run through one fixed-shape batched forward, and the rows stitched back per frame on the device.
+ *
+ * dbx_tile is one tile of a call's plan (64 bytes; offsets in brackets):
+ *   frame [0]             index of the frame the tile was cut from; the tiles of frame b are a contiguous range of the table
+ *   x0, y0 [4, 8]         window origin in the frame (>= 0): tile coordinate (x, y) is frame coordinate (x * scale + x0, y * scale + y0)
+ *   side [12]             window side in source pixels (`src`)
+ *   cw, ch [16, 20]       the part of the window inside the frame (min(side, W - x0), min(side, H - y0)); the rest of the window, on
+ *                         the right / bottom only, is constant padding of 128
+ *   scale [24]            src / tile as a double (tile: the network input side the window is resized to); < 1 magnifies
+ *   lo2x, hi2x, lo2y, hi2y [32, 40, 48, 56]   the tile's CORE, the part of the plane it owns, as DOUBLED coordinates so that the
+ *                         midpoint of an overlap is an integer: a box is owned iff lo2x <= x1 + x2 < hi2x and lo2y <= y1 + y2 < hi2y.
+ *                         The first core of an axis starts at -inf, the last ends at +inf; cores are half-open and partition the plane.
+ *
+ * dbx_tile_grid (HOST function, no GPU): the plan of ONE h x w frame for window side `src` and `overlap` (source pixels), row-major
+ * (y outer, x inner).  Along an axis of length L with stride D = src - overlap: L <= src gives one window at 0 (padded); otherwise
+ * n = ceil((L - src) / D) + 1 windows start at s_i = min(i * D, L - src) (the last one shifted inward, nothing padded).  The core
+ * boundary between windows i and i + 1 is m2_i = s_i + src + s_(i+1), the doubled midpoint of their overlap.  Writes frame = 0 and
+ * scale = 1 (the caller sets both) and returns the tile count; out == NULL returns the count alone.  Refused with DBX_ERR_ARG:
+ * src < 1, overlap < 0, 2 * overlap > src, h or w below 1, a non-null out with cap below the count, a plan of more than 2^20 tiles. */
+#define DBX_TILE_RULE_NONE 0
+#define DBX_TILE_RULE_CORE 1
+typedef struct dbx_tile {
+    int32_t frame, x0, y0, side, cw, ch;
+    double  scale, lo2x, hi2x, lo2y, hi2y;
+} dbx_tile;
+int dbx_tile_grid(int32_t h, int32_t w, int32_t src, int32_t overlap, dbx_tile* out, int32_t cap);
+
+/* The stitch.  `tiles` is the HOST table of the call's n_tiles tiles (checked before anything is queued), `tiles_dev` the caller's
+ * DEVICE copy of the same bytes, which the kernels read (as data: nothing in it is trusted as a bound).  `stage` is the call's staging
+ * area on the device, dbx_tile_stage_bytes(n_tiles, rows_per_tile, det_cols) bytes (-1 for counts out of range), in SLOT layout:
+ *   int32  [n_tiles][2]                          per tile (rows delivered, rows owned)            (rounded up to 256 bytes)
+ *   int32  [n_tiles][rows_per_tile]              the mark of every row: 1 owned, 0 not            (rounded up to 256 bytes)
+ *   double [n_tiles][rows_per_tile][det_cols]    the rows in source-frame coordinates
+ * Slots past a tile's delivered count are not written.
+ *
+ * dbx_tile_rows_batch, ONE launch per forward chunk: `rows` / `counts` are what dbx_detect_batch(K = rows_per_tile) -- rows
+ * [n][rows_per_tile][det_cols], counts NULL: every tile delivers rows_per_tile rows -- or dbx_thresh_rows_batch(max_dets =
+ * rows_per_tile) -- the same slot layout plus int32 counts [n][2], read on the device, clamped to 0..rows_per_tile and never trusted as
+ * a loop bound -- wrote for tiles t0 .. t0 + n - 1 of the table.  Every delivered row goes to its slot of `stage` with the x columns
+ * (0, 2, and 5, 7, 9, 11 when det_cols == 13) as x * scale - off_x, off_x = -x0, and the y columns alike, in float64 with the product
+ * rounded before the subtraction (NumPy's `d * scale - off` bit for bit); column 4, the score, is copied; NaN passes through.  The
+ * mark: under DBX_TILE_RULE_CORE the core test above on the MAPPED box in float64 (a NaN box is not owned); under DBX_TILE_RULE_NONE
+ * every row is owned.  `rows` may be overwritten as soon as the launch has run: stream order is the only synchronisation.
+ *
+ * dbx_tile_nms_batch, once per call behind the last chunk: frame b's tiles are the range [first_b, first_(b+1)) of the table (T_b may
+ * differ per frame); its owned rows are packed in tile order, then row order within the tile, and the reference's greedy NMS runs
+ * over them with dbx_nms_large's semantics and device code (score descending, the HIGHER packed row first among equal scores,
+ * !(ovr <= thresh) suppresses).  Three launches whose grids depend on (frames, n_tiles, rows_per_tile, the largest T_b) only: no host
+ * round trip, nothing polls, and the call may be captured.  Outputs (device), packed as dbx_merge_nms_thresh_batch packs:
+ *   out_counts  int32 [n_tiles][2]: the pairs of the staging area, then int32 [frames + 1]: P[b] = the owned rows of the frames before
+ *               b, P[frames] = the rows of the call.  2 * n_tiles + frames + 1 words.
+ *   out_dets    frame b's m_b owned rows start at row P[b].  Capacity n_tiles * rows_per_tile rows.
+ *   out_keep    frame b's list is m_b + 1 words at word P[b] + b: the count, then the kept row numbers within the frame's packed rows.
+ *               out_keep == (int32_t*)out_dets asks for the lists right BEHIND the packed rows, at byte P[frames] * det_cols * 8.
+ *   out_tile    int32, packed like the rows: the index in the table of the tile each row came from.
+ * A frame with no owned rows writes its pairs, its prefix word and a zero list count, and nothing else.
+ * workspace: dbx_tile_nms_batch_workspace_bytes(frames, max_tiles, rows_per_tile) bytes with max_tiles the largest T_b (-1 when
+ * max_tiles * rows_per_tile exceeds 4096 or a count is out of range).
+ * Refused with DBX_ERR_ARG before anything is queued: null pointers (counts excepted), n_tiles, n or frames below 1, t0 < 0 or
+ * t0 + n > n_tiles, det_cols other than 5 or 13, rows_per_tile outside 1..4096, a rule other than the two, any frame with
+ * T_b * rows_per_tile > 4096 (the NMS's bound), a tile with a scale that is not finite and positive, a negative origin or a NaN core
+ * bound, a table whose frame indices are not non-decreasing within 0..frames-1, a NaN or negative nms_thresh.
+ *
+ * dbx_tile_host runs the kernels' own mapping and ownership code on the CPU (no GPU needed): row i of rows [n][det_cols] is mapped by
+ * tiles[tile_of[i]] into out_rows [n][det_cols]; op 1 also writes its mark under `rule` to out_marks [n] (op 0: the map alone). */
+int64_t dbx_tile_stage_bytes(int32_t n_tiles, int32_t rows_per_tile, int32_t det_cols);
+int dbx_tile_rows_batch(const double* rows, const int32_t* counts, const dbx_tile* tiles, const dbx_tile* tiles_dev, int32_t n_tiles,
+                        int32_t t0, int32_t n, int32_t rows_per_tile, int32_t det_cols, int32_t rule, void* stage, void* stream);
+int64_t dbx_tile_nms_batch_workspace_bytes(int32_t frames, int32_t max_tiles, int32_t rows_per_tile);
+int dbx_tile_nms_batch(const dbx_tile* tiles, const dbx_tile* tiles_dev, int32_t n_tiles, int32_t frames, int32_t rows_per_tile,
+                       int32_t det_cols, double nms_thresh, const void* stage, double* out_dets, int32_t* out_keep, int32_t* out_tile,
+                       int32_t* out_counts, void* workspace, void* stream);
+int dbx_tile_host(int32_t op, int64_t n, const dbx_tile* tiles, int32_t n_tiles, const int32_t* tile_of, const double* rows,
+                  int32_t det_cols, int32_t rule, double* out_rows, int32_t* out_marks);
 
 /* ---- plate rectification after decode (perspective_transform, DenseBox.py:3446-3481; OpenCV's published algorithm) ----
  * dbx_perspective_matrix: host function, cv2.getPerspectiveTransform: 3x3 row-major double map src -> dst of four (x, y)
